@@ -19,6 +19,12 @@ config 3), ``impala`` the IMPALA V-trace one (config 5; ``--gpus N`` = N RCCL-jo
 learners), ``data`` the Ray Data → GPU ingest pipeline (config 4; ``--gpus N`` = N
 TorchTrainer workers consuming dataset shards) and ``microbench`` the task/actor
 call-rate microbenchmark (config 1). Prints ONE JSON line on rank 0.
+
+A plain run does what the headline figure needs and nothing else: set up, ``--warmup``
+untimed steps, exactly ``--steps`` timed steps (``ms_per_step`` is the time of one), the
+result line. ``--dump-outputs DIR`` adds the last timed step's outputs as ``DIR/*.npy``;
+``--full`` adds whatever goes beyond the headline figure (today: the long wait for a GPU
+that another process is still leaving).
 """
 
 from __future__ import annotations
@@ -87,9 +93,25 @@ def parse():
                          "ray_amd/tuned/<config>.csv; 'auto' uses that file if present")
     ap.add_argument("--device", default=None, help="gpt2: 'cpu' runs the launcher on gloo "
                     "(tests)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="gpt2: after the timed steps rank 0 writes what the last timed step "
+                         "returned and left behind as DIR/<name>.npy (ray_amd.train.examples."
+                         "gpt2.dump_outputs): loss, a fixed seeded sample of the fp32 master "
+                         "weights and of both AdamW moments, and the whole-buffer checksum. "
+                         "Tokens and initial weights are seeded, so two builds run with the "
+                         "same arguments can be compared output for output")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure. A plain run sets up, warms "
+                         "up, times --steps steps and prints the result line; with --full the "
+                         "run also waits for the GPU to settle for up to 120 s instead of 10 "
+                         "(RAY_AMD_BENCH_SETTLE_MAX_S overrides either)")
     args = ap.parse_args()
     if args.steps is None:
         args.steps = 300 if args.workload == "data" else 20
+    if args.dump_outputs is not None:
+        if args.workload != "gpt2":
+            ap.error("--dump-outputs is implemented for the gpt2 workload")
+        args.dump_outputs = os.path.abspath(args.dump_outputs)  # Train workers: own cwd
     return args
 
 
@@ -98,7 +120,7 @@ def _gpt2_config(args) -> dict:
                 steps=args.steps, warmup=args.warmup, grad_accum=args.grad_accum,
                 bucket_mb=args.bucket_mb, grad_dtype=args.grad_dtype, tunableop=args.tunableop,
                 lm_head_chunk=args.lm_head_chunk, device=args.device, ddp_hooks=args.ddp_hooks,
-                step_graph=args.step_graph == "on")
+                step_graph=args.step_graph == "on", dump_outputs=args.dump_outputs)
 
 
 def _emit(args, r: dict, mode: str, n_gpus: int):
@@ -142,6 +164,8 @@ def _emit(args, r: dict, mode: str, n_gpus: int):
         "wgrad_stream_autotune": r.get("wgrad_stream_autotune"),
         "hbm": r.get("hbm"),
         "gpu_settle_wait_s": _SETTLE_WAIT,
+        "full": args.full,
+        "dumped_outputs": r.get("dumped_outputs"),
     }
     # self-diagnosing multi-GPU runs: exposed comm, all-reduce launches / bytes and
     # per-bucket bus bandwidth per rank (FlatDDP.read_stats; zeros at world 1)
@@ -190,6 +214,13 @@ def bench_gpt2_bare(args):
         dist.destroy_process_group()
 
 
+def _storage_path() -> str:
+    # per user: a directory that another user of the machine created is not writable
+    import tempfile
+
+    return os.path.join(tempfile.gettempdir(), f"ray_amd_bench_{os.getuid()}")
+
+
 def bench_gpt2_ray(args):
     """Ray Train: TorchTrainer with ``--gpus`` GPU worker actors on an RCCL group.
 
@@ -226,7 +257,7 @@ def bench_gpt2_ray(args):
         trainer = TorchTrainer(
             train_func, train_loop_config=_gpt2_config(args),
             scaling_config=ScalingConfig(num_workers=args.gpus, use_gpu=use_gpu),
-            run_config=RunConfig(name="bench_gpt2", storage_path="/tmp/ray_amd_bench"))
+            run_config=RunConfig(name="bench_gpt2", storage_path=_storage_path()))
         result = trainer.fit()
         _emit(args, result.metrics, "ray_amd TorchTrainer", args.gpus)
     finally:
@@ -381,7 +412,10 @@ def main():
     profiled = any(k.startswith(("ROCPROF", "ROCP_")) for k in os.environ)
     if args.workload in ("gpt2", "allreduce") and args.device != "cpu" and not profiled and \
             os.environ.get("RAY_AMD_BENCH_SETTLE", "1") == "1":
-        _SETTLE_WAIT = _settle_gpu(float(os.environ.get("RAY_AMD_BENCH_SETTLE_MAX_S", "120")))
+        # a plain run keeps its time outside the steps short: it gives a busy GPU 10 s, and
+        # the warmup's stream autotune (run_steps) covers a box that has not settled by then
+        _SETTLE_WAIT = _settle_gpu(float(os.environ.get(
+            "RAY_AMD_BENCH_SETTLE_MAX_S", "120" if args.full else "10")))
     if args.workload == "gpt2":
         if args.no_ray:
             bench_gpt2_bare(args)

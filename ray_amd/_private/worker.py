@@ -22,7 +22,34 @@ SCRIPT_MODE = 0
 WORKER_MODE = 1
 LOCAL_MODE = 2
 
-ROOT_TMP = os.environ.get("RAY_AMD_TMPDIR", os.path.join(tempfile.gettempdir(), "ray_amd_sessions"))
+
+# A worker's socket is <root>/session_<19-char time>_<pid>_<6 hex>/sockets/<24 hex>.sock and
+# an AF_UNIX path holds 107 bytes: with a 7-digit pid that leaves the root 26.
+_ROOT_MAX = 107 - len("/session_2000-01-01_00-00-00_1234567_abcdef/sockets/") - 29
+
+
+def _session_root() -> str:
+    """Where session directories go: RAY_AMD_TMPDIR if set, else <tempdir>/ray_amd_sessions.
+    Two things change that default. A TMPDIR too long for the sockets (the raylet could not
+    bind) is replaced by /tmp. A ray_amd_sessions that another user created first is not
+    writable for this one, who then gets ray_amd_<uid> beside it. Both rules depend only on
+    lengths and on who owns the directory, so every process of a user finds the same root."""
+    if os.environ.get("RAY_AMD_TMPDIR"):
+        return os.environ["RAY_AMD_TMPDIR"]
+    base = tempfile.gettempdir()
+    if len(base) + len("/ray_amd_sessions") > _ROOT_MAX:
+        base = "/tmp"
+    shared = os.path.join(base, "ray_amd_sessions")
+    try:
+        ours = os.stat(shared).st_uid == os.getuid()
+    except FileNotFoundError:
+        ours = True  # whoever comes first creates it
+    except OSError:
+        ours = False
+    return shared if ours else os.path.join(base, f"ray_amd_{os.getuid()}")
+
+
+ROOT_TMP = _session_root()
 CURRENT_CLUSTER_FILE = os.path.join(ROOT_TMP, "ray_current_cluster")
 
 

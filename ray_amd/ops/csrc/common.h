@@ -97,9 +97,17 @@ __device__ __forceinline__ float block_max(float v, float* red) {
 constexpr int kColsumSplits = 32;
 namespace {  // internal linkage: every TU gets its own copy of these kernels
 
+// Up to three slabs go through one pair of launches: slab z (blockIdx.z of stage 1,
+// blockIdx.y of stage 2) is part + z * P * D, its scratch scratch + z * kColsumSplits * D.
+struct ColsumOuts {
+  void* p[3];
+};
+
 __global__ __launch_bounds__(256) void colsum_stage1(const float* __restrict__ part,
                                                      float* __restrict__ scratch, int P, int D) {
   __shared__ float red[4][64];
+  part += (size_t)blockIdx.z * P * D;
+  scratch += (size_t)blockIdx.z * kColsumSplits * D;
   const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
   const int c = blockIdx.x * 64 + tx;
   float s = 0.f;
@@ -115,10 +123,12 @@ __global__ __launch_bounds__(256) void colsum_stage1(const float* __restrict__ p
 // ACC: out += sum (parameter gradients accumulated in place into the flat grad buffer,
 // so autograd never launches a separate AccumulateGrad add)
 template <bool OUT_BF16, bool ACC>
-__global__ __launch_bounds__(256) void colsum_stage2(const float* __restrict__ scratch, void* out,
-                                                     int S, int D) {
+__global__ __launch_bounds__(256) void colsum_stage2(const float* __restrict__ scratch,
+                                                     ColsumOuts outs, int S, int D) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= D) return;
+  scratch += (size_t)blockIdx.y * kColsumSplits * D;
+  void* out = outs.p[blockIdx.y];
   float s = 0.f;
   for (int i = 0; i < S; ++i) s += scratch[(size_t)i * D + c];
   if (OUT_BF16) {
@@ -131,46 +141,37 @@ __global__ __launch_bounds__(256) void colsum_stage2(const float* __restrict__ s
   }
 }
 
-// fp32 destination: every stage-1 block adds its column sums straight into `out` with
-// float atomics (S*D adds, far below the atomic rate), so the tiny latency-bound second
-// launch disappears. Summation order across blocks is not fixed (last-bit nondeterminism).
-__global__ __launch_bounds__(256) void colsum_atomic(const float* __restrict__ part,
-                                                     float* __restrict__ out, int P, int D) {
-  __shared__ float red[4][64];
-  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-  const int c = blockIdx.x * 64 + tx;
-  float s = 0.f;
-  if (c < D) {
-    for (int p = blockIdx.y * 4 + ty; p < P; p += gridDim.y * 4) s += part[(size_t)p * D + c];
-  }
-  red[ty][tx] = s;
-  __syncthreads();
-  if (ty == 0 && c < D) atomicAdd(out + c, red[0][tx] + red[1][tx] + red[2][tx] + red[3][tx]);
-}
-
 }  // namespace
 
 namespace {
 
-// flags: bit0 = bf16 output, bit1 = accumulate into out. scratch: kColsumSplits * D floats.
+// flags: bit0 = bf16 output, bit1 = accumulate into out. n slabs (1..3) of [P, D] behind
+// one another in part; scratch: n * kColsumSplits * D floats. Both stages sum in a fixed
+// order (no float atomics): the same inputs give the same bits every run.
 enum { kColsumBF16 = 1, kColsumAcc = 2 };
-static inline void colsum_launch(const float* part, float* scratch, void* out, int P, int D,
-                                 int flags, hipStream_t st) {
+static inline void colsum_launch_n(const float* part, float* scratch, ColsumOuts outs, int n,
+                                   int P, int D, int flags, hipStream_t st) {
   int S = (P + 15) / 16;
   if (S > kColsumSplits) S = kColsumSplits;
   if (S < 1) S = 1;
-  if (!(flags & kColsumBF16)) {  // fp32 out: atomics, one pass
-    if (!(flags & kColsumAcc)) (void)hipMemsetAsync(out, 0, (size_t)D * sizeof(float), st);
-    hipLaunchKernelGGL(colsum_atomic, dim3((D + 63) / 64, S), dim3(256), 0, st, part,
-                       (float*)out, P, D);
-    return;
+  hipLaunchKernelGGL(colsum_stage1, dim3((D + 63) / 64, S, n), dim3(256), 0, st, part, scratch,
+                     P, D);
+  const dim3 g((D + 255) / 256, n), b(256);
+  if (flags & kColsumBF16) {
+    if (flags & kColsumAcc)
+      hipLaunchKernelGGL((colsum_stage2<true, true>), g, b, 0, st, scratch, outs, S, D);
+    else
+      hipLaunchKernelGGL((colsum_stage2<true, false>), g, b, 0, st, scratch, outs, S, D);
+  } else if (flags & kColsumAcc) {
+    hipLaunchKernelGGL((colsum_stage2<false, true>), g, b, 0, st, scratch, outs, S, D);
+  } else {
+    hipLaunchKernelGGL((colsum_stage2<false, false>), g, b, 0, st, scratch, outs, S, D);
   }
-  hipLaunchKernelGGL(colsum_stage1, dim3((D + 63) / 64, S), dim3(256), 0, st, part, scratch, P, D);
-  const dim3 g((D + 255) / 256), b(256);
-  if (flags & kColsumAcc)
-    hipLaunchKernelGGL((colsum_stage2<true, true>), g, b, 0, st, scratch, out, S, D);
-  else
-    hipLaunchKernelGGL((colsum_stage2<true, false>), g, b, 0, st, scratch, out, S, D);
+}
+
+static inline void colsum_launch(const float* part, float* scratch, void* out, int P, int D,
+                                 int flags, hipStream_t st) {
+  colsum_launch_n(part, scratch, ColsumOuts{{out, nullptr, nullptr}}, 1, P, D, flags, st);
 }
 
 }  // namespace

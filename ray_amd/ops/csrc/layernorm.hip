@@ -4,7 +4,7 @@
 // VPL x 4 elements in registers (8-byte bf16x4 loads), so the row is read from
 // HBM exactly once and mean/var are two in-register passes + wave shuffles.
 // Backward: each wave walks rows grid-stride, accumulating dgamma/dbeta per lane
-// in registers; waves combine through LDS atomics and write one fp32 partial row
+// in registers; waves combine through LDS in a fixed order and write one fp32 partial row
 // per block; `colsum_partials` finishes the column reduction.
 //
 // Replaces torch.nn.functional.layer_norm (used by GPT-2 blocks, reference
@@ -199,17 +199,23 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(
       }
     }
   }
+  // the four waves add their sums in turn, wave 0 first: a fixed order, so the same rows
+  // give the same bits every run (LDS float atomics add in whatever order the waves arrive)
+  for (int t = 0; t < 4; ++t) {
+    if (w == t) {
 #pragma unroll
-  for (int i = 0; i < VPL; ++i) {
-    const int col = (i * 64 + lane) * 4;
-    if (col < D) {
+      for (int i = 0; i < VPL; ++i) {
+        const int col = (i * 64 + lane) * 4;
+        if (col < D) {
 #pragma unroll
-      for (int k = 0; k < NP; ++k)
+          for (int k = 0; k < NP; ++k)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) atomicAdd(&lds[k * D + col + j], acc[k][i][j]);
+            for (int j = 0; j < 4; ++j) lds[k * D + col + j] += acc[k][i][j];
+        }
+      }
     }
+    __syncthreads();
   }
-  __syncthreads();
   const size_t P = gridDim.x;
   for (int i = threadIdx.x; i < NP * D; i += blockDim.x) {
     const int k = i / D, c = i - k * D;
@@ -250,7 +256,7 @@ __global__ __launch_bounds__(256) void ln_bwd2_kernel(
     const bf16_t* __restrict__ dy, const bf16_t* __restrict__ x, const bf16_t* __restrict__ g,
     const float* __restrict__ mean, const float* __restrict__ rstd,
     const bf16_t* __restrict__ dres, bf16_t* __restrict__ dx, float* __restrict__ part, int N,
-    int D, float* __restrict__ o0, float* __restrict__ o1, float* __restrict__ o2) {
+    int D) {
   extern __shared__ __attribute__((aligned(16))) float lds[];  // [NP][D]
   for (int i = threadIdx.x; i < NP * D; i += blockDim.x) lds[i] = 0.f;
   __syncthreads();
@@ -345,24 +351,20 @@ __global__ __launch_bounds__(256) void ln_bwd2_kernel(
       __builtin_amdgcn_sched_barrier(0);
     }
   }
+  // the four waves add their sums in turn, wave 0 first: a fixed order, so the same rows
+  // give the same bits every run (LDS float atomics add in whatever order the waves arrive)
+  for (int t = 0; t < 4; ++t) {
+    if (w == t) {
 #pragma unroll
-  for (int i = 0; i < VPL; ++i) {
-    const int col = (i * 64 + lane) * 4;
+      for (int i = 0; i < VPL; ++i) {
+        const int col = (i * 64 + lane) * 4;
 #pragma unroll
-    for (int k = 0; k < NP; ++k)
+        for (int k = 0; k < NP; ++k)
 #pragma unroll
-      for (int j = 0; j < 4; ++j) atomicAdd(&lds[k * D + col + j], acc[k][i][j]);
-  }
-  __syncthreads();
-  if (o0) {
-    // fp32 sinks accumulated in place (the flat gradient): the block's column sums go
-    // straight in with lane-linear float atomics (P adds per address, 256 contiguous bytes
-    // per wave instruction), instead of a partial slab and one colsum launch per sink
-    for (int i = threadIdx.x; i < NP * D; i += blockDim.x) {
-      const int k = i / D, c = i - k * D;
-      unsafeAtomicAdd((k == 0 ? o0 : k == 1 ? o1 : o2) + c, lds[i]);
+          for (int j = 0; j < 4; ++j) lds[k * D + col + j] += acc[k][i][j];
+      }
     }
-    return;
+    __syncthreads();
   }
   const size_t P = gridDim.x;
   for (int i = threadIdx.x; i < NP * D; i += blockDim.x) {
@@ -455,15 +457,14 @@ RA_EXPORT int ra_layernorm_bwd(const void* dy, const void* x, const void* g, con
   float* scr = work + (size_t)NP * P * D;
   const size_t lds = (size_t)NP * D * sizeof(float);
   if (ln_bwd_v2(N, D)) {
-    // fp32 sinks accumulated in place: column sums by atomics inside the kernel
-    const bool direct = !(flags & kColsumBF16) && (flags & kColsumAcc);
-    float* o0 = direct ? (float*)dg : nullptr;
-    float* o1 = direct ? (float*)db : nullptr;
-    float* o2 = direct ? (float*)dbias : nullptr;
+    // dg / db / dbias: partial slabs + fixed-order column sums. (Adding them straight into
+    // fp32 sinks with float atomics saved the colsum launches, but the order of those adds,
+    // and with it the gradients' last bits, changed from run to run; AdamW turns that into
+    // weights that differ after two steps.)
 #define L2K(V, NPV, R, KK)                                                                     \
   hipLaunchKernelGGL((ln_bwd2_kernel<V, NPV, R, KK>), dim3(P), dim3(256), lds, st,              \
                      (const bf16_t*)dy, (const bf16_t*)x, (const bf16_t*)g, mean, rstd,         \
-                     (const bf16_t*)dres, (bf16_t*)dx, work, N, D, o0, o1, o2)
+                     (const bf16_t*)dres, (bf16_t*)dx, work, N, D)
 #define L2(V, NPV, R) L2K(V, NPV, R, 2)
 #define L2V(V)                                       \
   if (NP == 3) {                                     \
@@ -480,11 +481,7 @@ RA_EXPORT int ra_layernorm_bwd(const void* dy, const void* x, const void* g, con
 #undef L2V
 #undef L2
 #undef L2K
-    if (direct) return hipGetLastError();
-    void* outs[3] = {dg, db, dbias};
-    for (int k = 0; k < NP; ++k)
-      colsum_launch(work + (size_t)k * P * D, scr + (size_t)k * kColsumSplits * D, outs[k], P,
-                    D, flags, st);
+    colsum_launch_n(work, scr, ColsumOuts{{dg, db, dbias}}, NP, P, D, flags, st);
     return hipGetLastError();
   }
 #define L(V)                                                                                  \
@@ -498,10 +495,7 @@ RA_EXPORT int ra_layernorm_bwd(const void* dy, const void* x, const void* g, con
                        (bf16_t*)dx, work, N, D);
   LN_DISPATCH(L)
 #undef L
-  void* outs[3] = {dg, db, dbias};
-  for (int k = 0; k < NP; ++k)
-    colsum_launch(work + (size_t)k * P * D, scr + (size_t)k * kColsumSplits * D, outs[k], P, D,
-                  flags, st);
+  colsum_launch_n(work, scr, ColsumOuts{{dg, db, dbias}}, NP, P, D, flags, st);
   return hipGetLastError();
 }
 

@@ -795,8 +795,14 @@ class _Embedding(torch.autograd.Function):
             # V = the table's row count (the sink may be a flat 1-D view of V*C floats).
             # Out-of-range ids never get here: F.embedding in the forward device-asserts on
             # them, as torch's index_add_ would; the kernel's bound check is a guard only.
-            check(_lib.lib().ra_embed_bwd(ptr(d2c), ptr(ids), ptr(sw), ptr(sp), B, T, C,
-                                          wte.shape[0], stream_ptr()), "embed_bwd")
+            # sorted ids: each token's rows are summed in a fixed order (no float atomics),
+            # so the same batch gives the same gradient bits every run
+            L = _lib.lib()
+            sid, perm = torch.sort(ids, stable=True)
+            work = torch.empty(L.ra_embed_bwd_work(B, T, C), device=dx.device,
+                               dtype=torch.float32)
+            check(L.ra_embed_bwd(ptr(d2c), ptr(sid), ptr(perm), ptr(work), ptr(sw), ptr(sp),
+                                 B, T, C, wte.shape[0], stream_ptr()), "embed_bwd")
             _grad_done(wte)
             _grad_done(wpe)
             return None, None, None

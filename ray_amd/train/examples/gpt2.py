@@ -46,8 +46,12 @@ def setup_tunableop(mode: str, src: str, rank: int):
 
     if mode == "off" or (mode == "auto" and not os.path.exists(src)):
         return "heuristic"
-    os.makedirs("/tmp/ray_amd_tunableop", exist_ok=True)
-    dst = f"/tmp/ray_amd_tunableop/{os.getpid()}_{rank}_{os.path.basename(src)}"
+    import tempfile
+
+    # per user: a directory that another user of the machine created is not writable
+    work = os.path.join(tempfile.gettempdir(), f"ray_amd_tunableop_{os.getuid()}")
+    os.makedirs(work, exist_ok=True)
+    dst = os.path.join(work, f"{os.getpid()}_{rank}_{os.path.basename(src)}")
     if os.path.exists(src):
         shutil.copyfile(src, dst)
     torch.cuda.tunable.enable(True)
@@ -100,6 +104,38 @@ def _master_checksum(p32):
         acc[0] += x.sum()
         acc[1] += (x * w).sum()
     return acc
+
+
+DUMP_SAMPLE = 1 << 20  # elements of each flat buffer written by dump_outputs
+
+
+def dump_outputs(tr, path: str) -> dict:
+    """Write what the last ``tr.step`` returned and left behind as ``path/<name>.npy``, so
+    two builds run with the same arguments can be compared output for output: the loss
+    (float32), the same fixed seeded sample of DUMP_SAMPLE positions of the fp32 master
+    weights and of both AdamW moments (float32; the buffers are ~0.5 GB each at GPT-2
+    small), the sampled positions and the whole-buffer master checksum (float64).
+    ~20 MB in all. Returns {name: shape}."""
+    import numpy as np
+    import torch
+
+    os.makedirs(path, exist_ok=True)
+    n = tr.flat.p32.numel()
+    g = torch.Generator(device="cpu")
+    g.manual_seed(20240)
+    idx = torch.randint(0, n, (min(DUMP_SAMPLE, n),), generator=g).sort().values
+    didx = idx.to(tr.flat.p32.device)
+    arrays = {
+        "loss": tr.last_loss.detach().float().reshape(1).cpu().numpy(),
+        "master_weights_sample": tr.flat.p32[didx].cpu().numpy(),
+        "adam_exp_avg_sample": tr.opt.m[didx].cpu().numpy(),
+        "adam_exp_avg_sq_sample": tr.opt.v[didx].cpu().numpy(),
+        "sample_index": idx.double().numpy(),
+        "master_checksum": _master_checksum(tr.flat.p32).cpu().numpy(),
+    }
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
 
 
 def run_steps(cfg: dict, device, rank: int, world: int) -> dict:
@@ -235,6 +271,9 @@ def run_steps(cfg: dict, device, rank: int, world: int) -> dict:
         in_sync = all(torch.equal(x, allc[0]) for x in allc)
     else:
         in_sync = True
+    dumped = None
+    if c.get("dump_outputs") and rank == 0:  # after the timed window; ranks hold one state
+        dumped = dump_outputs(tr, c["dump_outputs"])
     tokens = tr.tokens_per_step() * c["steps"]
     flops = tr.model.flops_per_token(c["seq_len"]) * tokens
     mem = None
@@ -267,6 +306,7 @@ def run_steps(cfg: dict, device, rank: int, world: int) -> dict:
         "ddp_stats": ddp_stats,
         "wgrad_stream_autotune": ab,
         "hbm": mem,
+        "dumped_outputs": dumped,
     }
 
 

@@ -67,7 +67,7 @@ def test_holder_peer_copy_path(small_arena, monkeypatch):
     assert gos.stats["peer_copies"] == before + 1 and torch.equal(v2, v)
 
 
-def test_train_worker_consumes_gpu_object_from_actor(small_arena):
+def test_train_worker_consumes_gpu_object_from_actor(small_arena, tmp_path):
     from ray_amd import train
     from ray_amd.train import RunConfig, ScalingConfig
     from ray_amd.train.torch import TorchTrainer
@@ -88,5 +88,5 @@ def test_train_worker_consumes_gpu_object_from_actor(small_arena):
     res = TorchTrainer(loop, train_loop_config={"refs": [ref]},
                        scaling_config=ScalingConfig(num_workers=1, use_gpu=True,
                                                     resources_per_worker={"GPU": 0.5}),
-                       run_config=RunConfig(storage_path="/tmp/ra_hbm_t")).fit()
+                       run_config=RunConfig(storage_path=str(tmp_path))).fit()
     assert res.metrics["cuda"] and res.metrics["sum"] == 2.0 * (1 << 18)

@@ -56,3 +56,35 @@ def test_log_to_driver_false_and_system_config(tmp_path):
     assert f"level {logging.DEBUG}" in r.stdout
     assert f"storage {tmp_path}" in r.stdout
     assert "in_files True" in r.stdout
+
+
+def test_session_root_fits_worker_sockets_and_is_ours(tmp_path, monkeypatch):
+    """Session directories go to <tempdir>/ray_amd_sessions unless the raylet and worker
+    sockets below it would not fit an AF_UNIX path (a long TMPDIR: /tmp instead) or another
+    user owns that directory (not writable for us: ray_amd_<uid> beside it instead).
+    RAY_AMD_TMPDIR is taken as given."""
+    import tempfile
+
+    from ray_amd._private import worker as W
+
+    sock = "/session_2000-01-01_00-00-00_1234567_abcdef/sockets/" + "0" * 24 + ".sock"
+    monkeypatch.delenv("RAY_AMD_TMPDIR", raising=False)
+    uid = os.getuid()
+    long_tmp = tmp_path / ("d" * 60)
+    long_tmp.mkdir()
+    monkeypatch.setattr(tempfile, "tempdir", str(long_tmp))
+    root = W._session_root()
+    assert root in ("/tmp/ray_amd_sessions", f"/tmp/ray_amd_{uid}")
+    assert len(root + sock) <= 107
+    # a temp dir that leaves room is used as it is; the shared name while nobody else owns it
+    short = str(tmp_path / "s")
+    os.mkdir(short)
+    monkeypatch.setattr(W, "_ROOT_MAX", len(short + "/ray_amd_sessions"))
+    monkeypatch.setattr(tempfile, "tempdir", short)
+    assert W._session_root() == short + "/ray_amd_sessions"
+    os.mkdir(short + "/ray_amd_sessions")
+    assert W._session_root() == short + "/ray_amd_sessions"  # ours
+    monkeypatch.setattr(os, "getuid", lambda: uid + 1)  # now it is another user's directory
+    assert W._session_root() == short + f"/ray_amd_{uid + 1}"
+    monkeypatch.setenv("RAY_AMD_TMPDIR", str(long_tmp))
+    assert W._session_root() == str(long_tmp)

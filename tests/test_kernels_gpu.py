@@ -720,7 +720,7 @@ def test_layernorm_bwd_v2_matches_fp32(cuda_device, N, D, res):
 @pytest.mark.parametrize("N,D,res", [(5003, 768, True), (65536, 768, False)])
 def test_layernorm_bwd_fp32_sinks_accumulate(cuda_device, N, D, res):
     """Flat-gradient contract of ra_layernorm_bwd (fp32 sinks, accumulate): dgamma, dbeta
-    and the residual-bias colsum are ADDED onto non-zero sinks by in-kernel atomics."""
+    and the residual-bias colsum are ADDED onto non-zero sinks (fixed-order column sums)."""
     from ray_amd.ops import _lib
     from ray_amd.ops._lib import check, ptr, stream_ptr
 
@@ -874,8 +874,9 @@ def test_linear_hip_wgrad_fused_bias_into_flat_sinks(cuda_device, monkeypatch):
 
 
 def test_embedding_backward_into_flat_sinks(cuda_device):
-    """ra_embed_bwd (ops/csrc/embed.hip): token-table scatter-add (duplicate ids included)
-    and position batch-sum into pre-filled fp32 sinks vs the fp32 torch reference."""
+    """ra_embed_bwd (ops/csrc/embed.hip): token-table scatter-add (duplicate ids included:
+    40 tokens over 768 rows, so most tokens span several 32-position chunks) and position
+    batch-sum into pre-filled fp32 sinks vs the fp32 torch reference."""
     torch.manual_seed(15)
     B, T, C, V, P = 8, 96, 768, 1000, 128
     idx = torch.randint(0, 40, (B, T), device=cuda_device)  # many duplicates

@@ -237,3 +237,41 @@ def test_accelerate_amp_keeps_state_dict_keys():
     buf.seek(0)
     again = torch.load(buf, weights_only=False)  # our own file
     assert again(torch.randn(2, 8)).dtype == torch.bfloat16
+
+
+def test_bench_dump_outputs_repeatable(tmp_path):
+    """bench.py --dump-outputs: the last timed step's outputs as float32/float64 .npy files,
+    at most 64 MB in all; the same arguments give the same inputs, so two CPU runs write
+    identical arrays. --steps sets the number of timed steps (one more step moves the
+    weights) and the result line carries ms_per_step."""
+    import subprocess
+    import sys
+
+    import numpy as np
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+    def run(name, steps):
+        cmd = [sys.executable, "bench.py", "--gpus", "1", "--no-ray", "--device", "cpu",
+               "--model", "tiny", "--micro-batch", "2", "--seq-len", "64", "--steps", str(steps),
+               "--warmup", "1", "--dump-outputs", str(tmp_path / name)]
+        env = dict(os.environ, OMP_NUM_THREADS="1")
+        r = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=300, env=env)
+        assert r.returncode == 0, r.stderr[-3000:]
+        j = _bench_json(r.stdout)
+        assert j["steps"] == steps and j["ms_per_step"] > 0 and j["full"] is False
+        files = sorted(os.listdir(tmp_path / name))
+        assert files == sorted(k + ".npy" for k in j["dumped_outputs"])
+        arrays = {f[:-4]: np.load(tmp_path / name / f) for f in files}
+        assert sum(os.path.getsize(tmp_path / name / f) for f in files) <= 64 << 20
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        assert all(np.isfinite(a).all() for a in arrays.values())
+        return arrays
+
+    a, b, c = run("a", 2), run("b", 2), run("c", 3)
+    assert {"loss", "master_weights_sample", "adam_exp_avg_sample", "adam_exp_avg_sq_sample",
+            "sample_index", "master_checksum"} == set(a)
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+    assert np.array_equal(a["sample_index"], c["sample_index"])
+    assert not np.array_equal(a["master_weights_sample"], c["master_weights_sample"])

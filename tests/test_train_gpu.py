@@ -154,7 +154,7 @@ def test_gpt2_trainer_fp32_vs_bf16_grads(cuda_device):
     assert abs(losses[torch.float32] - losses[torch.bfloat16]) < 0.1 * losses[torch.float32]
 
 
-def test_torchtrainer_gpt2_one_gpu(cuda_device):
+def test_torchtrainer_gpt2_one_gpu(cuda_device, tmp_path):
     """The headline launcher end to end: ray_amd.init -> TorchTrainer(1 GPU worker) ->
     GPT-2 (tiny) on the flat-DDP path -> train.report, RCCL group of size 1."""
     import ray_amd as ray
@@ -168,7 +168,7 @@ def test_torchtrainer_gpt2_one_gpu(cuda_device):
                    tunableop="off")
         res = TorchTrainer(train_func, train_loop_config=cfg,
                            scaling_config=ScalingConfig(num_workers=1, use_gpu=True),
-                           run_config=RunConfig(name="t_gpt2", storage_path="/tmp/ra_t")).fit()
+                           run_config=RunConfig(name="t_gpt2", storage_path=str(tmp_path))).fit()
         m = res.metrics
         assert m["device"].startswith("cuda")
         assert m["rccl_world_size"] == 1 and m["dist_backend"] == "nccl"
@@ -178,7 +178,7 @@ def test_torchtrainer_gpt2_one_gpu(cuda_device):
         ray.shutdown()
 
 
-def test_torchtrainer_gpt2_two_workers_one_gpu_gloo(cuda_device):
+def test_torchtrainer_gpt2_two_workers_one_gpu_gloo(cuda_device, tmp_path):
     """The world > 1 GPU path on a one-GPU box: two Train workers share the GPU
     (0.5 each) and join a gloo group (RCCL refuses two ranks on one device), so the flat
     DDP bucket hooks, the initial broadcast, the 1/world gradient scale and the
@@ -197,7 +197,7 @@ def test_torchtrainer_gpt2_two_workers_one_gpu_gloo(cuda_device):
                            scaling_config=ScalingConfig(num_workers=2, use_gpu=True,
                                                         resources_per_worker={"GPU": 0.5}),
                            run_config=RunConfig(name="t_gpt2_w2",
-                                                storage_path="/tmp/ra_t")).fit()
+                                                storage_path=str(tmp_path))).fit()
         m = res.metrics
         assert m["device"].startswith("cuda")
         assert m["rccl_world_size"] == 2 and m["dist_backend"] == "gloo"
@@ -413,3 +413,35 @@ def test_gpt2_small_bench_path_grads_match_fp32_autograd(cuda_device):
     # the side-stream wgrad kernel was on this path (not an eager fallback)
     assert rf._WGRAD_STREAM
     print("max rel err", max(worst))
+
+
+@pytest.mark.parametrize("model,B,T,chunk", [("tiny", 4, 128, 8192), ("small", 8, 1024, 4096)])
+def test_gpt2_training_steps_repeat_bitwise(cuda_device, model, B, T, chunk):
+    """Two trainers built from the same seed and fed the same batches end with the same bits
+    in loss, fp32 master weights and both AdamW moments: no kernel of the step sums in an
+    order that changes from run to run (duplicate token ids, LayerNorm and bias gradients
+    included). AdamW's normalised update would turn a last-bit difference in a gradient
+    into a visible weight difference within two steps. 'small' is the benchmark's model at a
+    smaller batch: the D = 768 LayerNorm backward, the weight-gradient side stream and a
+    chunked LM head; one token fills a fifth of its batch (many chunks of the embedding
+    backward)."""
+    from ray_amd.models.gpt2 import GPT2Config
+    from ray_amd.train.gpt2_step import GPT2Trainer
+
+    def run():
+        tr = GPT2Trainer(getattr(GPT2Config, model)(), B, T, cuda_device, total_steps=3, seed=7,
+                         lm_head_chunk=chunk)
+        gen = torch.Generator(device=cuda_device)
+        gen.manual_seed(11)
+        x, y = tr.synthetic_batch(gen)
+        x[:, :T // 5] = x[0, 0]
+        losses = [float(tr.step([(x, y)])) for _ in range(3)]
+        torch.cuda.synchronize(cuda_device)
+        out = losses, tr.flat.p32.clone(), tr.opt.m.clone(), tr.opt.v.clone()
+        del tr
+        return out
+
+    a, b = run(), run()
+    assert a[0] == b[0]
+    for u, v in zip(a[1:], b[1:]):
+        assert torch.equal(u, v)
