@@ -940,6 +940,66 @@ def ppo_loss(logits, old_logits, actions, old_logp, adv, vpred, vtarg, clip=0.2,
     return _PPOLoss.apply(logits, vpred, old_logits, actions, old_logp, adv, vtarg, hp)
 
 
+def c51_loss_forward(logits, actions, next_online, next_target, rewards, discounts, terminateds,
+                     weights=None, v_min=-10.0, v_max=10.0, with_target=False):
+    """The raw outputs of the fused C51 kernel (HIP tensors, 2 <= K <= 64): (loss, ce [B],
+    next_action [B] int32, dlogits [B, A, K] = d loss / d logits, target_dist [B, K] or
+    None). ``c51_loss`` is the autograd entry point over this."""
+    B, A, K = logits.shape
+    dev = logits.device
+
+    def f32(t):
+        return None if t is None else t.detach().float().contiguous()
+
+    ce = torch.empty(B, device=dev, dtype=torch.float32)
+    loss = torch.empty((), device=dev, dtype=torch.float32)
+    dlogits = torch.empty(B, A, K, device=dev, dtype=torch.float32)
+    na = torch.empty(B, device=dev, dtype=torch.int32)
+    m = torch.empty(B, K, device=dev, dtype=torch.float32) if with_target else None
+    if not torch.is_tensor(discounts):
+        discounts = torch.full((B,), float(discounts), device=dev)
+    lg, no, nt, r, d, t, w = map(f32, (logits, next_online, next_target, rewards, discounts,
+                                       terminateds, weights))
+    act = actions.long().contiguous()
+    check(_lib.lib().ra_c51_loss(
+        ptr(lg), ptr(act), ptr(no), ptr(nt), ptr(r), ptr(d), ptr(t), ptr(w), ptr(ce),
+        ptr(dlogits), ptr(na), ptr(m), ptr(loss), B, A, K, float(v_min), float(v_max),
+        stream_ptr()), "c51_loss")
+    return loss, ce, na, dlogits, m
+
+
+class _C51Loss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, actions, next_online, next_target, rewards, discounts, terminateds,
+                weights, v_min, v_max):
+        loss, ce, na, dlogits, _ = c51_loss_forward(
+            logits, actions, next_online, next_target, rewards, discounts, terminateds, weights,
+            v_min, v_max)
+        ctx.save_for_backward(dlogits)
+        ctx.dtype = logits.dtype
+        ctx.mark_non_differentiable(ce, na)
+        return loss, ce, na
+
+    @staticmethod
+    def backward(ctx, g, _gce, _gna):
+        (dlogits,) = ctx.saved_tensors
+        return ((dlogits * g).to(ctx.dtype),) + (None,) * 9
+
+
+def c51_loss(logits, actions, next_online, next_target, rewards, discounts, terminateds,
+             weights=None, v_min=-10.0, v_max=10.0):
+    """Fused distributional (C51) DQN loss on [B, A, K] atom logits: returns (loss, per-row
+    cross-entropy [B], greedy next action [B]). ``next_online`` None selects the next action
+    with ``next_target`` (no double-Q). One kernel computes the projected target, the
+    loss AND its gradient wrt ``logits`` (the only differentiable input); 2 <= K <= 64."""
+    B, A, K = logits.shape
+    if not _hip(logits) or K > 64 or K < 2:
+        return ref.c51_loss(logits, actions, next_online, next_target, rewards, discounts,
+                            terminateds, weights, v_min, v_max)[:3]
+    return _C51Loss.apply(logits, actions, next_online, next_target, rewards, discounts,
+                          terminateds, weights, float(v_min), float(v_max))
+
+
 def ppo_pack(old_logits, actions, old_logp, adv, vtarg):
     """The behaviour-side PPO fields of a whole train batch as ONE fp32 table
     [N, A+4] = [old_logits | action | old_logp | adv | vtarg] for ``ppo_loss_packed``

@@ -104,6 +104,51 @@ def ppo_loss(logits, old_logits, actions, old_logp, adv, vpred, vtarg, clip=0.2,
     return total, stats
 
 
+def _c51_support(K, v_min, v_max, like):
+    dz = (v_max - v_min) / (K - 1)
+    return v_min + dz * torch.arange(K, device=like.device, dtype=like.dtype), dz
+
+
+def c51_project(p, rewards, discounts, terminateds, v_min, v_max):
+    """Categorical projection of the Bellman-shifted distribution onto the fixed support
+    (Bellemare et al. 2017, Algorithm 1; reference: dqn_torch_learner.py): atom j of
+    ``p`` [B, K] moves to clamp(r + disc (1 - term) z_j) and its mass is split between
+    the two neighbouring atoms (floor / ceil + scatter_add). A target landing exactly on
+    an atom (l == u) keeps its whole mass there. Computes in p's dtype."""
+    K = p.shape[-1]
+    z, dz = _c51_support(K, v_min, v_max, p)
+    r, d, t = (torch.as_tensor(x, device=p.device).to(p.dtype).expand(p.shape[0])[:, None]
+               for x in (rewards, discounts, terminateds))
+    tz = (r + d * (1.0 - t) * z[None]).clamp(v_min, v_max)
+    b = ((tz - v_min) / dz).clamp(0, K - 1)
+    lo, up = b.floor(), b.ceil()
+    m = torch.zeros_like(p)
+    m.scatter_add_(1, lo.long(), p * (up - b + (lo == up).to(p.dtype)))
+    m.scatter_add_(1, up.long(), p * (b - lo))
+    return m
+
+
+def c51_loss(logits, actions, next_online, next_target, rewards, discounts, terminateds,
+             weights=None, v_min=-10.0, v_max=10.0):
+    """Distributional (C51) DQN loss on [B, A, K] atom logits: the greedy next action is
+    taken under ``next_online`` (double-Q; None: under ``next_target``), the target
+    net's distribution of that action is projected (``c51_project``) and the loss is the
+    importance-weighted mean cross-entropy against the taken action's distribution.
+    Returns (loss, per-row ce, next_action, projected target [B, K])."""
+    B, _, K = logits.shape
+    rows = torch.arange(B, device=logits.device)
+    with torch.no_grad():
+        sel = next_target if next_online is None else next_online
+        z, _ = _c51_support(K, v_min, v_max, sel)
+        na = (torch.softmax(sel, -1) * z).sum(-1).argmax(-1)
+        m = c51_project(torch.softmax(next_target, -1)[rows, na], rewards, discounts,
+                        terminateds, v_min, v_max).to(logits.dtype)
+    lp = torch.log_softmax(logits, -1)[rows, actions.long()]
+    ce = -(m * lp).sum(-1)
+    loss = ce.mean() if weights is None else (ce * weights.to(ce.dtype)).mean()
+    return loss, ce.detach(), na, m
+
+
 def image_normalize(x_u8_nhwc, mean, std, out_dtype=torch.float32):
     x = x_u8_nhwc.float().div(255.0).permute(0, 3, 1, 2)
     m = torch.as_tensor(mean, dtype=torch.float32, device=x.device).view(1, -1, 1, 1)

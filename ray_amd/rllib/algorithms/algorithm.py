@@ -818,11 +818,9 @@ class Algorithm:
         """An inference module of this algorithm's kind (what its EnvRunners run)."""
         kind = self.cfg.get("module_kind", "actor_critic")
         if kind == "q":
-            from ray_amd.rllib.core.rl_module import QModule
+            from ray_amd.rllib.core.rl_module import QModule, q_model_config
 
-            mc = dict(self.config.model or {})
-            mc["dueling"] = self.cfg.get("dueling", True)
-            return QModule(obs_space, act_space, mc)
+            return QModule(obs_space, act_space, q_model_config(self.cfg, self.config.model))
         if kind == "sac":
             from ray_amd.rllib.core.rl_module import SquashedGaussianPolicy
 

@@ -1,4 +1,5 @@
-"""DQN (double, dueling, prioritized replay, n-step=1) (reference: rllib/algorithms/dqn/)."""
+"""DQN up to Rainbow (double, dueling, prioritized replay, n-step, distributional C51 head,
+noisy nets) (reference: rllib/algorithms/dqn/)."""
 
 from __future__ import annotations
 
@@ -10,7 +11,7 @@ from ray_amd.rllib.algorithms.algorithm import (Algorithm, PerModuleLearners, ad
                                                  flat_transitions)
 from ray_amd.rllib.algorithms.algorithm_config import AlgorithmConfig
 from ray_amd.rllib.core.learner import LearnerGroup, TorchLearner
-from ray_amd.rllib.core.rl_module import QModule
+from ray_amd.rllib.core.rl_module import QModule, q_model_config
 from ray_amd.rllib.utils.replay_buffers import PrioritizedReplayBuffer, ReplayBuffer
 
 
@@ -32,6 +33,32 @@ class DQNConfig(AlgorithmConfig):
         self.grad_clip = 40.0
         self.model = {"fcnet_hiddens": [256], "fcnet_activation": "relu"}
         self.n_step = 1
+        # Rainbow: num_atoms > 1 = distributional (C51) head over linspace(v_min, v_max,
+        # num_atoms) trained by the fused projection loss; noisy = NoisyLinear heads and
+        # hidden layers (sigma0 their initial noise scale) instead of epsilon-greedy
+        self.num_atoms = 1
+        self.v_min = -10.0
+        self.v_max = 10.0
+        self.noisy = False
+        self.sigma0 = 0.5
+
+    def validate(self):
+        super().validate()
+        if int(self.num_atoms) < 1:
+            raise ValueError(f"num_atoms must be >= 1, got {self.num_atoms}")
+        if not float(self.v_min) < float(self.v_max):
+            raise ValueError(f"v_min ({self.v_min}) must be below v_max ({self.v_max})")
+        return True
+
+    def epsilon_schedule(self):
+        """The epsilon-greedy schedule in effect: noisy nets explore through their
+        parameter noise, so with ``noisy`` and an untouched ``epsilon`` it is all zero."""
+        if self.noisy and [tuple(x) for x in self.epsilon] == list(_DEFAULT_EPSILON):
+            return [(0, 0.0)]
+        return self.epsilon
+
+
+_DEFAULT_EPSILON = ((0, 1.0), (10000, 0.05))
 
 
 class DQNLearner(TorchLearner):
@@ -42,8 +69,7 @@ class DQNLearner(TorchLearner):
     prioritized replay buffer. ``num_learners=N``: N learners on 1/N of each batch."""
 
     def build_module(self):
-        mc = dict(self.config.get("model") or {})
-        mc["dueling"] = self.config.get("dueling", True)
+        mc = q_model_config(self.config)
         m = torch.nn.ModuleDict({"q": QModule(self.observation_space, self.action_space, mc),
                                  "target": QModule(self.observation_space, self.action_space,
                                                    mc)})
@@ -56,8 +82,39 @@ class DQNLearner(TorchLearner):
         self.register_optimizer(module_id=module_id, optimizer=torch.optim.Adam(
             params, lr=config.get("lr", 5e-4)), params=params)
 
+    def _forward_train_dist(self, b):
+        """num_atoms > 1: the three atom-logit tensors [B, A, K] of the C51 loss."""
+        q, target = self.module["q"], self.module["target"]
+        q.reset_noise()  # noisy nets: one noise draw per update, per network
+        target.reset_noise()
+        out = {"logits": q.forward_dist(b["obs"])}
+        with torch.no_grad():
+            nobs = b["next_obs"]
+            out["next_target"] = target.forward_dist(nobs)
+            out["next_online"] = q.forward_dist(nobs) if self.config.get("double_q", True) \
+                else None
+        return out
+
+    def _c51_loss(self, batch, fwd_out):
+        from ray_amd.ops import functional as rf
+
+        n = len(batch["rewards"])
+        disc = batch["discounts"].float() if "discounts" in batch else torch.full(
+            (n,), float(self.config.get("gamma", 0.99)), device=fwd_out["logits"].device)
+        w = batch.get("weights")
+        q = self.module["q"]
+        loss, ce, _ = rf.c51_loss(
+            fwd_out["logits"].float(), batch["actions"].long(), fwd_out["next_online"],
+            fwd_out["next_target"].float(), batch["rewards"].float(), disc,
+            batch["terminateds"].float(), w.float() if w is not None else None,
+            q.v_min, q.v_max)
+        self._td = ce.detach()  # the cross-entropy is the priority (reference: Rainbow)
+        return loss
+
     def forward_train(self, b):
         q = self.module["q"]
+        if q.num_atoms > 1:
+            return self._forward_train_dist(b)
         qa = q(b["obs"]).gather(-1, b["actions"].long()[:, None])[:, 0]
         with torch.no_grad():
             nobs = b["next_obs"]
@@ -72,6 +129,8 @@ class DQNLearner(TorchLearner):
         return {"q": qa, "target": tgt}
 
     def compute_loss_for_module(self, *, module_id, config, batch, fwd_out):
+        if "logits" in fwd_out:
+            return self._c51_loss(batch, fwd_out)
         q, tgt = fwd_out["q"], fwd_out["target"]
         w = batch.get("weights")
         self._td = (q - tgt).detach()
@@ -113,6 +172,7 @@ class DQN(Algorithm):
         t = t if isinstance(t, str) else getattr(t, "__name__", "")
         self.episodic = t == "EpisodeReplayBuffer" and not config.is_multi_agent
         config._record_episodes = self.episodic
+        config.validate()
         super().__init__(config)
 
     @classmethod
@@ -167,7 +227,7 @@ class DQN(Algorithm):
                 stats[f"{mid}/loss"] = res["loss"]
 
     def _epsilon(self):
-        sched = self.config.epsilon
+        sched = self.config.epsilon_schedule()
         t = self.total_env_steps
         (t0, e0), (t1, e1) = sched[0], sched[-1]
         if t >= t1:

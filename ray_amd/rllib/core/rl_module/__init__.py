@@ -6,9 +6,10 @@ fast paths, Q-network, SAC actor/critics); ``rl_module`` the user-extensibility 
 uses. This package's namespace binds no ``torch`` name, so the ``torch`` subpackage
 (reference path ``rl_module.torch.TorchRLModule``) can be imported safely."""
 
-from ray_amd.rllib.core.rl_module.default import (MLP, NatureCNN, QModule,  # noqa: F401
-                                                  RLModule, SquashedGaussianPolicy, TwinQ,
-                                                  gaussian_entropy, gaussian_logp)
+from ray_amd.rllib.core.rl_module.default import (MLP, NatureCNN, NoisyLinear,  # noqa: F401
+                                                  QModule, RLModule, SquashedGaussianPolicy,
+                                                  TwinQ, gaussian_entropy, gaussian_logp,
+                                                  q_model_config)
 from ray_amd.rllib.core.rl_module.rl_module import (MultiRLModuleSpec,  # noqa: F401
                                                     RLModuleSpec, TorchRLModule,
                                                     ValueFunctionAPI, build_module)

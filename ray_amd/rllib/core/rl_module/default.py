@@ -27,13 +27,54 @@ def _act(name):
             "elu": nn.ELU}.get(name or "tanh", nn.Tanh)
 
 
+class NoisyLinear(nn.Module):
+    """Linear layer with factorised Gaussian parameter noise (Fortunato et al. 2018,
+    "Noisy Networks for Exploration"; reference: rllib/algorithms/dqn/torch/
+    torch_noisy_linear.py): w = weight_mu + weight_sigma * (f(e_out) f(e_in)^T),
+    b = bias_mu + bias_sigma * f(e_out), f(x) = sign(x) sqrt|x|, sigma = sigma0 / sqrt(in).
+    Training forwards, and eval forwards while ``explore`` is set (the env runners'
+    exploring rollouts), use the noisy parameters; other eval forwards use mu only.
+    The noise stays fixed until ``reset_noise()`` and is not part of the state dict."""
+
+    def __init__(self, in_features, out_features, sigma0=0.5):
+        super().__init__()
+        self.in_features, self.out_features, self.sigma0 = in_features, out_features, sigma0
+        self.explore = False
+        self.weight_mu = nn.Parameter(torch.empty(out_features, in_features))
+        self.weight_sigma = nn.Parameter(torch.empty(out_features, in_features))
+        self.bias_mu = nn.Parameter(torch.empty(out_features))
+        self.bias_sigma = nn.Parameter(torch.empty(out_features))
+        self.register_buffer("eps_in", torch.zeros(in_features), persistent=False)
+        self.register_buffer("eps_out", torch.zeros(out_features), persistent=False)
+        bound = 1.0 / math.sqrt(in_features)
+        nn.init.uniform_(self.weight_mu, -bound, bound)
+        nn.init.uniform_(self.bias_mu, -bound, bound)
+        nn.init.constant_(self.weight_sigma, sigma0 * bound)
+        nn.init.constant_(self.bias_sigma, sigma0 * bound)
+        self.reset_noise()
+
+    @staticmethod
+    def _f(x):
+        return x.sign() * x.abs().sqrt()
+
+    def reset_noise(self):
+        self.eps_in.copy_(self._f(torch.randn_like(self.eps_in)))
+        self.eps_out.copy_(self._f(torch.randn_like(self.eps_out)))
+
+    def forward(self, x):
+        if not (self.training or self.explore):
+            return F.linear(x, self.weight_mu, self.bias_mu)
+        w = self.weight_mu + self.weight_sigma * torch.outer(self.eps_out, self.eps_in)
+        return F.linear(x, w, self.bias_mu + self.bias_sigma * self.eps_out)
+
+
 class MLP(nn.Module):
-    def __init__(self, in_dim, hiddens, activation="tanh"):
+    def __init__(self, in_dim, hiddens, activation="tanh", linear=nn.Linear):
         super().__init__()
         layers = []
         d = in_dim
         for h in hiddens:
-            layers += [nn.Linear(d, h), _act(activation)()]
+            layers += [linear(d, h), _act(activation)()]
             d = h
         self.net = nn.Sequential(*layers)
         self.out_dim = d
@@ -211,8 +252,30 @@ def gaussian_entropy(log_std):
     return (log_std.clamp(-20, 2) + 0.5 * math.log(2 * math.pi * math.e)).sum(-1)
 
 
+Q_MODEL_KEYS = ("dueling", "num_atoms", "v_min", "v_max", "noisy", "sigma0")
+
+
+def q_model_config(config, model=None) -> dict:
+    """The QModule model config of a DQN config (dict or DQNConfig): its ``model`` dict
+    plus the algorithm-level keys the Q network is built from. The learner, the env
+    runners and ``Algorithm.get_module`` all build their QModule from this."""
+    mc = dict((config.get("model") if model is None else model) or {})
+    mc["dueling"] = config.get("dueling", True)
+    for k in Q_MODEL_KEYS[1:]:
+        v = config.get(k)
+        if v is not None:
+            mc[k] = v
+    return mc
+
+
 class QModule(nn.Module):
-    """Q-network (optionally dueling) for DQN (reference: rllib/algorithms/dqn)."""
+    """Q-network (optionally dueling) for DQN (reference: rllib/algorithms/dqn).
+
+    ``num_atoms`` K > 1 makes it distributional (C51): the heads output K atom logits per
+    action over the support linspace(v_min, v_max, K); ``forward_dist`` returns the logits
+    [B, A, K] (dueling per atom: v + a - mean_a a) and ``forward`` the expected Q-values
+    [B, A], so greedy action selection is unchanged. ``noisy`` builds the heads and the
+    MLP's hidden layers from ``NoisyLinear`` (``reset_noise`` / ``set_explore``)."""
 
     def __init__(self, observation_space, action_space, model_config=None):
         super().__init__()
@@ -220,22 +283,57 @@ class QModule(nn.Module):
         obs_shape = tuple(observation_space.shape)
         self.is_image = len(obs_shape) == 3
         self.dueling = cfg.get("dueling", True)
+        self.num_atoms = int(cfg.get("num_atoms", 1) or 1)
+        self.noisy = bool(cfg.get("noisy", False))
+        sigma0 = float(cfg.get("sigma0", 0.5))
+        linear = (lambda i, o: NoisyLinear(i, o, sigma0)) if self.noisy else nn.Linear
         if self.is_image:
             self.encoder = NatureCNN(obs_shape)
         else:
             self.encoder = MLP(int(np.prod(obs_shape)), cfg.get("fcnet_hiddens", [256, 256]),
-                               cfg.get("fcnet_activation", "relu"))
-        n = action_space.n
-        self.adv = nn.Linear(self.encoder.out_dim, n)
-        self.val = nn.Linear(self.encoder.out_dim, 1) if self.dueling else None
+                               cfg.get("fcnet_activation", "relu"), linear)
+        n = self.n_actions = action_space.n
+        K = self.num_atoms
+        self.adv = linear(self.encoder.out_dim, n * K)
+        self.val = linear(self.encoder.out_dim, K) if self.dueling else None
+        if K > 1:
+            self.v_min, self.v_max = float(cfg.get("v_min", -10.0)), float(cfg.get("v_max", 10.0))
+            self.register_buffer("support", torch.linspace(self.v_min, self.v_max, K))
+
+    def _hidden(self, obs):
+        x = obs if self.is_image else obs.reshape(obs.shape[0], -1).float()
+        return self.encoder(x)
+
+    def forward_dist(self, obs):
+        """Atom logits [B, A, K] (num_atoms > 1)."""
+        h = self._hidden(obs)
+        a = self.adv(h).view(-1, self.n_actions, self.num_atoms)
+        if self.val is None:
+            return a
+        return self.val(h)[:, None, :] + a - a.mean(1, keepdim=True)
 
     def forward(self, obs):
-        x = obs if self.is_image else obs.reshape(obs.shape[0], -1).float()
-        h = self.encoder(x)
+        if self.num_atoms > 1:
+            return (torch.softmax(self.forward_dist(obs).float(), -1) * self.support).sum(-1)
+        h = self._hidden(obs)
         a = self.adv(h)
         if self.val is None:
             return a
         return self.val(h) + a - a.mean(-1, keepdim=True)
+
+    def reset_noise(self):
+        """New noise in every NoisyLinear layer (no-op without ``noisy``)."""
+        if self.noisy:
+            for m in self.modules():
+                if isinstance(m, NoisyLinear):
+                    m.reset_noise()
+
+    def set_explore(self, explore: bool):
+        """Noisy parameters in eval-mode forwards (exploring rollouts) on / off."""
+        if self.noisy:
+            for m in self.modules():
+                if isinstance(m, NoisyLinear):
+                    m.explore = bool(explore)
 
 
 class SquashedGaussianPolicy(nn.Module):

@@ -90,11 +90,9 @@ class MultiAgentEnvRunner:
 
     def _make_module(self, os_, as_, mid=None):
         if self.module_kind == "q":  # multi-agent DQN: epsilon-greedy over Q-values
-            from ray_amd.rllib.core.rl_module import QModule
+            from ray_amd.rllib.core.rl_module import QModule, q_model_config
 
-            mc = dict(self.config.get("model") or {})
-            mc["dueling"] = self.config.get("dueling", True)
-            return QModule(os_, as_, mc)
+            return QModule(os_, as_, q_model_config(self.config))
         if self.module_kind == "sac":  # multi-agent SAC: the squashed-Gaussian actor
             from ray_amd.rllib.core.rl_module import SquashedGaussianPolicy
 
@@ -107,6 +105,9 @@ class MultiAgentEnvRunner:
     def _act(self, mod, x, explore, epsilon, as_):
         """(actions, logp, dist inputs) for a stacked observation batch."""
         if self.module_kind == "q":
+            if getattr(mod, "noisy", False):  # noisy nets explore through parameter noise
+                mod.set_explore(explore)
+                mod.reset_noise()
             q = mod(x).float()
             a = q.argmax(-1).numpy()
             if explore and epsilon:
