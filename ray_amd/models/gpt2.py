@@ -21,6 +21,11 @@ MI355X-first choices:
   (weights, biases, LayerNorm) accumulated in place into the flat DDP gradient
   buffer (no AccumulateGrad adds); the residual stream's two gradients are summed
   inside the LayerNorm backward kernel (``LayerNorm.fork``).
+* Generation: ``prefill`` (flash attention over the right-padded prompts, K/V copied into
+  a ``KVCache``, LM head on each row's last position only) and ``decode_step`` (one token
+  per row through the HIP decode-attention kernel, ops/csrc/attn_decode.hip, with the
+  row lengths kept on the device: no host sync, one HIP-graph capture serves every
+  position); ``generate`` drives them.
 """
 
 from __future__ import annotations
@@ -119,6 +124,44 @@ class Block(nn.Module):
         return rf.bias_residual(self.mlp(h), self.mlp_proj_b, x)
 
 
+class KVCache:
+    """Per-layer K/V of a batch of sequences for ``GPT2.prefill`` / ``decode_step``:
+    ``k``, ``v`` [n_layer, B, H, max_len, head_dim] and ``lens`` int32 [B], the positions
+    cached per row (kept on the device: the decode kernel reads it there)."""
+
+    def __init__(self, cfg: GPT2Config, batch: int, max_len: int, device=None, dtype=None):
+        if max_len < 1 or max_len > cfg.n_positions:
+            raise ValueError(f"max_len must be in 1..{cfg.n_positions}, got {max_len}")
+        shape = (cfg.n_layer, batch, cfg.n_head, max_len, cfg.n_embd // cfg.n_head)
+        self.k = torch.zeros(shape, device=device, dtype=dtype)
+        self.v = torch.zeros(shape, device=device, dtype=dtype)
+        self.lens = torch.zeros(batch, device=device, dtype=torch.int32)
+        self.max_len = max_len
+
+
+class _GraphedStep:
+    """``decode_step`` captured once in a HIP graph (one stream, no parallel branches) with
+    static token and logits buffers; ``cache.lens`` lives on the device and is advanced
+    inside the graph, so every replay is the step for the next position."""
+
+    def __init__(self, model, cache, tok):
+        from ray_amd.ops.graph_lock import CAPTURE_LOCK
+
+        self.tok = tok.clone()
+        torch.cuda.synchronize(tok.device)
+        self.graph = torch.cuda.CUDAGraph()
+        with CAPTURE_LOCK, torch.no_grad(), torch.cuda.graph(self.graph):
+            self.logits = model.decode_step(self.tok, cache)
+
+    def __call__(self, tok):
+        from ray_amd.ops.graph_lock import CAPTURE_LOCK
+
+        self.tok.copy_(tok)
+        with CAPTURE_LOCK:
+            self.graph.replay()
+        return self.logits
+
+
 class GPT2(nn.Module):
     def __init__(self, cfg: GPT2Config):
         super().__init__()
@@ -169,6 +212,133 @@ class GPT2(nn.Module):
         # embedding backward, which runs last, signals wte's DDP readiness
         return rf.lm_head_cross_entropy(h, self.wte, targets, self.cfg.vocab_size,
                                         chunk=self.lm_head_chunk, signal_w=False)
+
+    # ------------------------------------------------------------------ generation
+    def _flash_ok(self, x) -> bool:
+        return x.is_cuda and x.dtype == torch.bfloat16 and \
+            self.cfg.n_embd // self.cfg.n_head == 64
+
+    @torch.no_grad()
+    def prefill(self, idx, lens, cache: KVCache):
+        """Runs the right-padded prompts ``idx`` [B, T] (true lengths ``lens`` [B], >= 1)
+        through the model, stores every layer's K/V in ``cache`` and returns the logits of
+        each row's last real token, [B, vocab_size]. Causal attention keeps the padding
+        out of the real positions; the padded positions' K/V are leftovers that the decode
+        kernel masks out and overwrites."""
+        cfg = self.cfg
+        B, T = idx.shape
+        H, hd = cfg.n_head, cfg.n_embd // cfg.n_head
+        if B != cache.k.shape[1]:
+            raise ValueError(f"cache holds {cache.k.shape[1]} rows, prompts have {B}")
+        lens = torch.as_tensor(lens, device=idx.device).to(torch.int32)
+        Tp = T
+        if self._flash_ok(self.wte) and T % 128 and -(-T // 128) * 128 <= cfg.n_positions:
+            # the MFMA flash kernel wants T % 128 == 0; more right padding is as harmless
+            Tp = -(-T // 128) * 128
+            idx = F.pad(idx, (0, Tp - T))
+        n = min(T, cache.max_len)
+        x = rf.embedding(idx, self.wte, self.wpe)
+        x, h = self.h[0].ln_1.fork(x)
+        for i, blk in enumerate(self.h):
+            qkv = F.linear(h, blk.c_attn_w, blk.c_attn_b).view(B, Tp, 3, H, hd)
+            cache.k[i, :, :, :n].copy_(qkv[:, :n, 1].transpose(1, 2))
+            cache.v[i, :, :, :n].copy_(qkv[:, :n, 2].transpose(1, 2))
+            y = rf.causal_attention_qkv(qkv)
+            a = F.linear(y.reshape(B, Tp, cfg.n_embd), blk.c_proj_w)
+            x, h = rf.residual_layer_norm(a, blk.c_proj_b, x, blk.ln_2.weight, blk.ln_2.bias,
+                                          blk.ln_2.eps)
+            nxt = self.h[i + 1].ln_1 if i + 1 < len(self.h) else self.ln_f
+            m = F.linear(rf.bias_gelu(F.linear(h, blk.c_fc_w), blk.c_fc_b), blk.mlp_proj_w)
+            x, h = rf.residual_layer_norm(m, blk.mlp_proj_b, x, nxt.weight, nxt.bias, nxt.eps)
+        # only the last real position of each row meets the LM head: [B, C] x [C, V]
+        last = (lens.long() - 1).clamp(0, Tp - 1)
+        hl = h[torch.arange(B, device=idx.device), last]
+        cache.lens = lens.clone()
+        return F.linear(hl, self.wte)[:, : cfg.vocab_size]
+
+    @torch.no_grad()
+    def decode_step(self, tok, cache: KVCache):
+        """One token per row: ``tok`` [B] is the token at position ``cache.lens[b]``;
+        appends its K/V to the cache, returns the next-token logits [B, vocab_size] and
+        advances ``cache.lens``. No host synchronisation: capturable in a HIP graph, and
+        one capture serves every position."""
+        cfg = self.cfg
+        B = tok.shape[0]
+        H, hd = cfg.n_head, cfg.n_embd // cfg.n_head
+        pos = cache.lens.long().clamp(0, cfg.n_positions - 1)
+        x = self.wte[tok] + self.wpe[pos]
+        x, h = self.h[0].ln_1.fork(x)
+        for i, blk in enumerate(self.h):
+            qkv = F.linear(h, blk.c_attn_w, blk.c_attn_b).view(B, 3, H, hd)
+            y = rf.attn_decode(qkv, cache.k[i], cache.v[i], cache.lens)
+            a = F.linear(y.view(B, cfg.n_embd), blk.c_proj_w)
+            x, h = rf.residual_layer_norm(a, blk.c_proj_b, x, blk.ln_2.weight, blk.ln_2.bias,
+                                          blk.ln_2.eps)
+            nxt = self.h[i + 1].ln_1 if i + 1 < len(self.h) else self.ln_f
+            m = F.linear(rf.bias_gelu(F.linear(h, blk.c_fc_w), blk.c_fc_b), blk.mlp_proj_w)
+            x, h = rf.residual_layer_norm(m, blk.mlp_proj_b, x, nxt.weight, nxt.bias, nxt.eps)
+        logits = F.linear(h, self.wte)[:, : cfg.vocab_size]
+        cache.lens += 1
+        return logits
+
+    @staticmethod
+    def _pick(logits, temperature, top_k, generator):
+        if temperature == 0.0:
+            return logits.argmax(-1)
+        lg = logits.float() / temperature
+        if top_k is not None:
+            kth = lg.topk(min(int(top_k), lg.shape[-1]), -1).values[:, -1:]
+            lg = lg.masked_fill(lg < kth, float("-inf"))
+        return torch.multinomial(torch.softmax(lg, -1), 1, generator=generator).squeeze(1)
+
+    @torch.no_grad()
+    def generate(self, idx, max_new_tokens, *, lens=None, temperature=0.0, top_k=None,
+                 eos_token_id=None, generator=None, graph=False):
+        """Autoregressive generation with a KV cache: ``idx`` [B, T] prompts, right-padded
+        to a common length with true lengths ``lens`` (default: all T). Returns the new
+        tokens [B, max_new_tokens] (int64). ``temperature`` 0 is greedy, otherwise samples
+        softmax(logits / temperature) over the ``top_k`` largest with ``generator``. A row
+        that emits ``eos_token_id`` keeps emitting it. ``graph=True`` (GPU) captures one
+        ``decode_step`` in a HIP graph and replays it per token; sampling stays outside,
+        so the tokens are those of the eager loop."""
+        cfg = self.cfg
+        B, T = idx.shape
+        lens_l = [T] * B if lens is None else [int(v) for v in torch.as_tensor(lens).tolist()]
+        if B == 0 or T == 0 or len(lens_l) != B or min(lens_l) < 1:
+            raise ValueError("generate needs a non-empty prompt in every row")
+        if max(lens_l) > T:
+            raise ValueError(f"lens {max(lens_l)} exceeds the prompt width {T}")
+        if max_new_tokens < 1:
+            raise ValueError("max_new_tokens must be >= 1")
+        if max(lens_l) + max_new_tokens > cfg.n_positions:
+            raise ValueError(f"prompt ({max(lens_l)}) + max_new_tokens ({max_new_tokens}) "
+                             f"exceeds n_positions ({cfg.n_positions})")
+        if temperature < 0:
+            raise ValueError("temperature must be >= 0")
+        if graph and not idx.is_cuda:
+            raise ValueError("graph=True needs the model and prompts on the GPU")
+        dev = idx.device
+        cache = KVCache(cfg, B, max(lens_l) + max_new_tokens, dev, self.wte.dtype)
+        logits = self.prefill(idx, torch.tensor(lens_l, dtype=torch.int32, device=dev), cache)
+        out = torch.empty(B, max_new_tokens, dtype=torch.long, device=dev)
+        done = torch.zeros(B, dtype=torch.bool, device=dev)
+        step = None
+        for t in range(max_new_tokens):
+            tok = self._pick(logits, float(temperature), top_k, generator)
+            if eos_token_id is not None:
+                tok = torch.where(done, torch.full_like(tok, eos_token_id), tok)
+                done |= tok == eos_token_id
+            out[:, t] = tok
+            if t + 1 == max_new_tokens:
+                break
+            if not graph or t == 0:
+                # (graph: the first step runs eagerly and warms up what the capture needs)
+                logits = self.decode_step(tok, cache)
+            else:
+                if step is None:
+                    step = _GraphedStep(self, cache, tok)
+                logits = step(tok)
+        return out
 
     def flops_per_token(self, T: int) -> float:
         """6N + 12·L·H·hd·T (PaLM appendix B convention), training FLOPs per token."""

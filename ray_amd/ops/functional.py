@@ -603,6 +603,48 @@ def causal_attention_qkv(qkv, scale=None):
     return y.transpose(1, 2)
 
 
+def attn_decode(qkv_new, k_cache, v_cache, lens, scale=None, splits=None):
+    """One decode step of attention: appends the new token's k/v (``qkv_new`` [B, 3, H, D],
+    the packed c_attn output) to ``k_cache`` / ``v_cache`` [B, H, Tmax, D] IN PLACE at
+    position ``lens[b]`` and returns the attention of its q over positions 0..lens[b],
+    [B, H, D]. ``lens`` (int32 [B], on the tensors' device) is only read, on the device —
+    the caller advances it — so the call is graph-capturable and one capture serves every
+    position. Rows with lens[b] outside [0, Tmax) are inactive: no write, zero output.
+
+    HIP split-KV kernel for bf16, D == 64 (``splits``: None / 0 automatic, or an explicit
+    count); CPU tensors, other dtypes and other head sizes use the plain-torch reference.
+    Inference only: raises on tensors that require grad."""
+    if qkv_new.requires_grad or k_cache.requires_grad or v_cache.requires_grad:
+        raise RuntimeError("attn_decode is an inference op: run it under torch.no_grad() on "
+                           "tensors that do not require grad")
+    if qkv_new.dim() != 4 or qkv_new.shape[1] != 3:
+        raise ValueError(f"qkv_new must be [B, 3, H, D], got {tuple(qkv_new.shape)}")
+    B, _, H, D = qkv_new.shape
+    if k_cache.shape != v_cache.shape or k_cache.dim() != 4 or \
+            k_cache.shape[:2] != (B, H) or k_cache.shape[3] != D or lens.shape != (B,):
+        raise ValueError("attn_decode: caches must be [B, H, Tmax, D] and lens [B]")
+    if scale is None:
+        scale = D ** -0.5
+    if not (_hip(qkv_new) and qkv_new.dtype == torch.bfloat16 and D == 64
+            and k_cache.dtype == torch.bfloat16 and v_cache.dtype == torch.bfloat16):
+        return ref.attn_decode(qkv_new, k_cache, v_cache, lens, scale)
+    if lens.dtype != torch.int32 or not lens.is_cuda:
+        raise ValueError("attn_decode: lens must be an int32 tensor on the GPU")
+    if not (k_cache.is_contiguous() and v_cache.is_contiguous()):
+        raise ValueError("attn_decode: the caches are written in place and must be contiguous")
+    Tmax = k_cache.shape[2]
+    S = int(splits or 0)
+    L = _lib.lib()
+    qkv_new = qkv_new.contiguous()
+    lens = lens.contiguous()
+    out = torch.empty((B, H, D), device=qkv_new.device, dtype=torch.bfloat16)
+    nws = L.ra_attn_decode_work(B, H, Tmax, S)
+    ws = torch.empty(nws, device=qkv_new.device, dtype=torch.float32) if nws else None
+    check(L.ra_attn_decode(ptr(qkv_new), ptr(k_cache), ptr(v_cache), ptr(lens), ptr(out), ptr(ws),
+                           B, H, Tmax, float(scale), S, stream_ptr()), "attn_decode")
+    return out
+
+
 # --------------------------------------------------------------------- cross entropy
 class _CrossEntropy(torch.autograd.Function):
     @staticmethod

@@ -38,6 +38,35 @@ def cross_entropy(logits, targets, vocab_size=None, ignore_index=-100):
     return F.cross_entropy(lf, targets.reshape(-1), ignore_index=ignore_index)
 
 
+def attn_decode(qkv_new, k_cache, v_cache, lens, scale=None):
+    """Single-query attention over a K/V cache (ops/csrc/attn_decode.hip semantics).
+
+    ``qkv_new`` [B, 3, H, D] is the new token's packed q/k/v, the caches are
+    [B, H, Tmax, D], ``lens`` [B] the cached positions per row. A row with
+    0 <= lens[b] < Tmax gets k/v written IN PLACE at position lens[b] and attends over
+    0..lens[b]; any other row is inactive (cache untouched, zero output). Positions past
+    lens[b] are masked out whatever they hold (NaN included). fp32 math, no host sync."""
+    B, _, H, D = qkv_new.shape
+    Tmax = k_cache.shape[2]
+    if scale is None:
+        scale = D ** -0.5
+    q, k, v = qkv_new.unbind(1)
+    lens = lens.long()
+    active = (lens >= 0) & (lens < Tmax)
+    idx = lens.clamp(0, Tmax - 1).view(B, 1, 1, 1).expand(B, H, 1, D)
+    act = active.view(B, 1, 1, 1)
+    for cache, new in ((k_cache, k), (v_cache, v)):
+        cache.scatter_(2, idx, torch.where(act, new.unsqueeze(2).to(cache.dtype),
+                                           cache.gather(2, idx)))
+    t = torch.arange(Tmax, device=lens.device)
+    keep = ((t.view(1, 1, Tmax) <= lens.view(B, 1, 1)) & active.view(B, 1, 1)).expand(B, H, Tmax)
+    s = (q.float().unsqueeze(2) @ k_cache.float().transpose(-1, -2)).squeeze(2) * scale
+    p = torch.softmax(s.masked_fill(~keep, float("-inf")), -1)
+    p = torch.where(keep, p, torch.zeros_like(p))  # inactive rows: softmax of all -inf
+    vf = torch.where(keep.unsqueeze(-1), v_cache.float(), torch.zeros((), device=s.device))
+    return (p.unsqueeze(2) @ vf).squeeze(2).to(qkv_new.dtype)
+
+
 def _f(x):
     return x.to(torch.promote_types(x.dtype, torch.float32))
 
