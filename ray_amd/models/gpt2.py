@@ -25,7 +25,9 @@ MI355X-first choices:
   a ``KVCache``, LM head on each row's last position only) and ``decode_step`` (one token
   per row through the HIP decode-attention kernel, ops/csrc/attn_decode.hip, with the
   row lengths kept on the device: no host sync, one HIP-graph capture serves every
-  position); ``generate`` drives them.
+  position); ``generate`` drives them. With ``seeds=`` the next token comes from the HIP
+  sampler (ops/csrc/sample.hip: temperature, top-k, top-p and seed per row, one launch, no
+  host sync) and the whole step, sampler included, is one graph replay.
 """
 
 from __future__ import annotations
@@ -162,6 +164,78 @@ class _GraphedStep:
         return self.logits
 
 
+class _SeededSampler:
+    """The device-sampler step of ``generate(seeds=...)``: draws a token per row from the
+    static logits buffer with per-row parameters (``rf.sample_logits``: the hash step is
+    ``cache.lens[b]``, the position of the token being drawn, EOS latching fused), writes
+    it into column ``col`` of ``out`` (``col`` lives on the device) and runs
+    ``decode_step`` back into the logits buffer. Nothing in it touches the host, so
+    ``capture`` records the whole step in ONE HIP graph (one stream, no parallel branches)
+    and a token then costs one replay."""
+
+    def __init__(self, model, cache, logits, out, temperature, top_k, top_p, seeds, eos):
+        cfg = model.cfg
+        dev = out.device
+        B = out.shape[0]
+        self.model, self.cache, self.out, self.eos = model, cache, out, eos
+        self.buf = torch.empty(B, cfg.padded_vocab, device=dev, dtype=logits.dtype)
+        self.logits = self.buf[:, : cfg.vocab_size]
+        self.logits.copy_(logits)
+        self.temperature = torch.tensor(temperature, dtype=torch.float32, device=dev)
+        self.top_k = torch.tensor(top_k, dtype=torch.int32, device=dev)
+        self.top_p = torch.tensor(top_p, dtype=torch.float32, device=dev)
+        self.seeds = torch.tensor(seeds, dtype=torch.int64, device=dev)
+        self.done = torch.zeros(B, dtype=torch.uint8, device=dev)
+        self.col = torch.zeros(1, 1, dtype=torch.long, device=dev)
+        self.tok = None  # the sampler's output (inside a capture: the graph's static buffer)
+        self.graph = None
+
+    def _step(self):
+        self.tok = rf.sample_logits(self.logits, self.temperature, self.top_k, self.top_p,
+                                    self.seeds, self.cache.lens, done=self.done,
+                                    eos_token_id=self.eos, validate=False)
+        self.out.scatter_(1, self.col.expand(self.out.shape[0], 1), self.tok.unsqueeze(1))
+        self.col += 1
+        self.model.decode_step(self.tok, self.cache, out=self.buf)
+
+    def draw_last(self):
+        """The last token of a call needs no ``decode_step`` after it."""
+        tok = rf.sample_logits(self.logits, self.temperature, self.top_k, self.top_p,
+                               self.seeds, self.cache.lens, done=self.done,
+                               eos_token_id=self.eos, validate=False)
+        self.out.scatter_(1, self.col.expand(self.out.shape[0], 1), tok.unsqueeze(1))
+
+    def capture(self):
+        from ray_amd.ops.graph_lock import CAPTURE_LOCK
+
+        torch.cuda.synchronize(self.out.device)
+        self.graph = torch.cuda.CUDAGraph()
+        with CAPTURE_LOCK, torch.no_grad(), torch.cuda.graph(self.graph):
+            self._step()
+
+    def __call__(self):
+        if self.graph is None:
+            self._step()
+        else:
+            from ray_amd.ops.graph_lock import CAPTURE_LOCK
+
+            with CAPTURE_LOCK:
+                self.graph.replay()
+
+
+def _per_row(name, value, default, B, cast):
+    """``value`` (None, a scalar or a per-row sequence) as a list of B ``cast`` values."""
+    if value is None:
+        value = default
+    if isinstance(value, torch.Tensor):
+        value = value.tolist()
+    if isinstance(value, (list, tuple)):
+        if len(value) != B:
+            raise ValueError(f"{name} has {len(value)} entries for {B} rows")
+        return [cast(default if v is None else v) for v in value]
+    return [cast(value)] * B
+
+
 class GPT2(nn.Module):
     def __init__(self, cfg: GPT2Config):
         super().__init__()
@@ -257,11 +331,13 @@ class GPT2(nn.Module):
         return F.linear(hl, self.wte)[:, : cfg.vocab_size]
 
     @torch.no_grad()
-    def decode_step(self, tok, cache: KVCache):
+    def decode_step(self, tok, cache: KVCache, out=None):
         """One token per row: ``tok`` [B] is the token at position ``cache.lens[b]``;
         appends its K/V to the cache, returns the next-token logits [B, vocab_size] and
         advances ``cache.lens``. No host synchronisation: capturable in a HIP graph, and
-        one capture serves every position."""
+        one capture serves every position. ``out`` [B, padded_vocab]: the LM head writes
+        there and the result is a view of it (a graph whose next replay reads the logits
+        needs them at a fixed address)."""
         cfg = self.cfg
         B = tok.shape[0]
         H, hd = cfg.n_head, cfg.n_embd // cfg.n_head
@@ -277,7 +353,10 @@ class GPT2(nn.Module):
             nxt = self.h[i + 1].ln_1 if i + 1 < len(self.h) else self.ln_f
             m = F.linear(rf.bias_gelu(F.linear(h, blk.c_fc_w), blk.c_fc_b), blk.mlp_proj_w)
             x, h = rf.residual_layer_norm(m, blk.mlp_proj_b, x, nxt.weight, nxt.bias, nxt.eps)
-        logits = F.linear(h, self.wte)[:, : cfg.vocab_size]
+        if out is None:
+            logits = F.linear(h, self.wte)[:, : cfg.vocab_size]
+        else:
+            logits = torch.mm(h, self.wte.t(), out=out)[:, : cfg.vocab_size]
         cache.lens += 1
         return logits
 
@@ -293,16 +372,32 @@ class GPT2(nn.Module):
 
     @torch.no_grad()
     def generate(self, idx, max_new_tokens, *, lens=None, temperature=0.0, top_k=None,
-                 eos_token_id=None, generator=None, graph=False):
+                 top_p=None, seeds=None, eos_token_id=None, generator=None, graph=False):
         """Autoregressive generation with a KV cache: ``idx`` [B, T] prompts, right-padded
         to a common length with true lengths ``lens`` (default: all T). Returns the new
         tokens [B, max_new_tokens] (int64). ``temperature`` 0 is greedy, otherwise samples
         softmax(logits / temperature) over the ``top_k`` largest with ``generator``. A row
         that emits ``eos_token_id`` keeps emitting it. ``graph=True`` (GPU) captures one
         ``decode_step`` in a HIP graph and replays it per token; sampling stays outside,
-        so the tokens are those of the eager loop."""
+        so the tokens are those of the eager loop.
+
+        ``seeds`` (an int, or one per row) selects the device sampler
+        (``rf.sample_logits``): ``temperature``, ``top_k`` and ``top_p`` may then be scalars
+        or per-row sequences (0 / None / None switch a rule off), and the randomness of a
+        token is a hash of the row's seed and the token's position, so a row's tokens
+        depend on its prompt, its parameters and its seed only, never on its batch-mates.
+        With ``graph=True`` the sampler, the EOS latch and the write into the result are
+        captured with ``decode_step``: a token costs one graph replay and nothing else."""
         cfg = self.cfg
         B, T = idx.shape
+        if seeds is None:
+            if top_p is not None:
+                raise ValueError("top_p needs the device sampler: pass seeds=")
+            if any(isinstance(v, (list, tuple, torch.Tensor)) for v in (temperature, top_k)):
+                raise ValueError("per-row temperature / top_k need the device sampler: pass "
+                                 "seeds=")
+        elif generator is not None:
+            raise ValueError("seeds and generator are two sources of randomness: pass one")
         lens_l = [T] * B if lens is None else [int(v) for v in torch.as_tensor(lens).tolist()]
         if B == 0 or T == 0 or len(lens_l) != B or min(lens_l) < 1:
             raise ValueError("generate needs a non-empty prompt in every row")
@@ -313,7 +408,19 @@ class GPT2(nn.Module):
         if max(lens_l) + max_new_tokens > cfg.n_positions:
             raise ValueError(f"prompt ({max(lens_l)}) + max_new_tokens ({max_new_tokens}) "
                              f"exceeds n_positions ({cfg.n_positions})")
-        if temperature < 0:
+        if seeds is not None:
+            temps = _per_row("temperature", temperature, 0.0, B, float)
+            ks = _per_row("top_k", top_k, 0, B, int)
+            ps = _per_row("top_p", top_p, 1.0, B, float)
+            seeds_l = _per_row("seeds", seeds, 0, B, int)
+            if min(temps) < 0 or any(t != t for t in temps):
+                raise ValueError("temperature must be >= 0")
+            if any(not p > 0 for p in ps):
+                raise ValueError("top_p must be > 0")
+            if any(not -2 ** 63 <= v < 2 ** 64 for v in seeds_l):
+                raise ValueError("seeds must fit 64 bits")
+            seeds_l = [v - 2 ** 64 if v >= 2 ** 63 else v for v in seeds_l]
+        elif temperature < 0:
             raise ValueError("temperature must be >= 0")
         if graph and not idx.is_cuda:
             raise ValueError("graph=True needs the model and prompts on the GPU")
@@ -321,6 +428,23 @@ class GPT2(nn.Module):
         cache = KVCache(cfg, B, max(lens_l) + max_new_tokens, dev, self.wte.dtype)
         logits = self.prefill(idx, torch.tensor(lens_l, dtype=torch.int32, device=dev), cache)
         out = torch.empty(B, max_new_tokens, dtype=torch.long, device=dev)
+        if seeds is not None:
+            eos = None if eos_token_id is None else int(eos_token_id)
+            step = _SeededSampler(self, cache, logits, out, temps, ks, ps, seeds_l, eos)
+            if max_new_tokens > 1:
+                step()
+                if graph:
+                    # (the first step ran eagerly and warmed up what the capture needs.) The
+                    # last replay's decode_step is spare: its position is still inside the
+                    # cache, and the loop stays free of any launch but the replay
+                    step.capture()
+                    for _ in range(max_new_tokens - 1):
+                        step()
+                    return out
+                for _ in range(max_new_tokens - 2):
+                    step()
+            step.draw_last()
+            return out
         done = torch.zeros(B, dtype=torch.bool, device=dev)
         step = None
         for t in range(max_new_tokens):

@@ -645,6 +645,71 @@ def attn_decode(qkv_new, k_cache, v_cache, lens, scale=None, splits=None):
     return out
 
 
+SAMPLE_MAX_VOCAB = 1 << 18  # ops/csrc/sample.hip kMaxV (checked against the library)
+
+
+def sample_logits(logits, temperature, top_k, top_p, seeds, steps, vocab_size=None, done=None,
+                  eos_token_id=None, validate=True):
+    """One token per row of ``logits`` [B, Vs] (the first ``vocab_size or Vs`` columns count)
+    with per-row ``temperature`` fp32, ``top_k`` int32, ``top_p`` fp32, ``seeds`` int64 and
+    ``steps`` int32, all [B] on the logits' device; the randomness is a hash of (seed, step).
+    Semantics: ``reference.sample_logits``. Returns int64 [B].
+
+    ``done`` (uint8 [B], optional, updated IN PLACE) with ``eos_token_id``: a row whose
+    ``done`` is set emits ``eos_token_id``, a row that draws it sets ``done``.
+
+    HIP kernel (one launch, every parameter read on the device, no host sync: capturable
+    and one capture serves every position) for GPU tensors with bf16 logits of unit column
+    stride and at most ``SAMPLE_MAX_VOCAB`` = 262144 columns (GPT-2's 50257 included); the
+    rows may be a column slice of a wider buffer, which is read in place. CPU tensors,
+    other dtypes and wider vocabularies use the plain-torch reference."""
+    if logits.dim() != 2:
+        raise ValueError(f"sample_logits: logits must be [B, V], got {tuple(logits.shape)}")
+    B, Vs = logits.shape
+    V = Vs if vocab_size is None else int(vocab_size)
+    if B < 1 or V < 1 or V > Vs:
+        raise ValueError(f"sample_logits: vocab_size {V} does not fit logits {tuple(logits.shape)}")
+    if not logits.dtype.is_floating_point:
+        raise ValueError("sample_logits: logits must be floating point")
+    for name, t, dt in (("temperature", temperature, torch.float32),
+                        ("top_k", top_k, torch.int32), ("top_p", top_p, torch.float32),
+                        ("seeds", seeds, torch.int64), ("steps", steps, torch.int32)):
+        if not isinstance(t, torch.Tensor) or t.shape != (B,) or t.dtype != dt or \
+                t.device != logits.device:
+            raise ValueError(f"sample_logits: {name} must be a {dt} tensor of shape [{B}] on "
+                             f"{logits.device}")
+    use_eos = done is not None and eos_token_id is not None and int(eos_token_id) >= 0
+    if done is not None and (done.shape != (B,) or done.dtype != torch.uint8
+                             or done.device != logits.device):
+        raise ValueError(f"sample_logits: done must be a uint8 tensor of shape [{B}]")
+    hip = _hip(logits) and logits.dtype == torch.bfloat16 and V <= SAMPLE_MAX_VOCAB
+    if validate and not (hip and torch.cuda.is_current_stream_capturing()):
+        # the one host read of this function: callers that checked their temperatures on
+        # the host pass validate=False (a capture skips it, it could not run there)
+        if bool((temperature < 0).any()):
+            raise ValueError("sample_logits: temperature must be >= 0")
+    if not hip:
+        tok = ref.sample_logits(logits, temperature, top_k, top_p, seeds, steps, V)
+        if use_eos:
+            tok = torch.where(done.bool(), torch.full_like(tok, int(eos_token_id)), tok)
+            done |= (tok == int(eos_token_id)).to(torch.uint8)
+        return tok
+    L = _lib.lib()
+    assert L.ra_sample_logits_max_v() == SAMPLE_MAX_VOCAB
+    if logits.stride(1) != 1 or (B > 1 and logits.stride(0) < V):
+        logits = logits.contiguous()
+    if use_eos and not done.is_contiguous():
+        raise ValueError("sample_logits: done is written in place and must be contiguous")
+    tok = torch.empty(B, device=logits.device, dtype=torch.int64)
+    check(L.ra_sample_logits(ptr(logits), max(logits.stride(0), V), ptr(temperature.contiguous()),
+                             ptr(top_k.contiguous()), ptr(top_p.contiguous()),
+                             ptr(seeds.contiguous()), ptr(steps.contiguous()),
+                             ptr(done) if use_eos else None,
+                             int(eos_token_id) if use_eos else -1, ptr(tok), B, V,
+                             stream_ptr()), "sample_logits")
+    return tok
+
+
 # --------------------------------------------------------------------- cross entropy
 class _CrossEntropy(torch.autograd.Function):
     @staticmethod

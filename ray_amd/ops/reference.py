@@ -67,6 +67,94 @@ def attn_decode(qkv_new, k_cache, v_cache, lens, scale=None):
     return (p.unsqueeze(2) @ vf).squeeze(2).to(qkv_new.dtype)
 
 
+_MASK64 = (1 << 64) - 1
+
+
+def _i64(c):
+    """The 64-bit constant ``c`` as the int64 with the same bits."""
+    c &= _MASK64
+    return c - (1 << 64) if c >> 63 else c
+
+
+def _lsr(z, n):
+    """Logical shift right of int64 bit patterns."""
+    return (z >> n) & ((1 << (64 - n)) - 1)
+
+
+def sample_uniform(seeds, steps, dtype=torch.float32):
+    """The sampler's counter-based uniform in [0, 1): ``(splitmix64(seed, step) >> 40) *
+    2**-24`` with ``z = seed + (step + 1) * 0x9E3779B97F4A7C15`` mixed by the splitmix64
+    finaliser, all mod 2**64 (int64 tensors wrap the same way). ``seeds`` int64 [B],
+    ``steps`` integer [B]."""
+    z = seeds.to(torch.int64) + (steps.to(torch.int64) + 1) * _i64(0x9E3779B97F4A7C15)
+    z = (z ^ _lsr(z, 30)) * _i64(0xBF58476D1CE4E5B9)
+    z = (z ^ _lsr(z, 27)) * _i64(0x94D049BB133111EB)
+    z = z ^ _lsr(z, 31)
+    return _lsr(z, 40).to(dtype) * 2.0 ** -24
+
+
+def _sample_logits_u(logits, temperature, top_k, top_p, u, vocab_size=None,
+                     dtype=torch.float32):
+    """``sample_logits`` with the uniforms ``u`` [B] given; the math runs in ``dtype``."""
+    V = vocab_size or logits.shape[-1]
+    x = logits[:, :V].to(dtype)  # the stored values, exactly
+    dev = x.device
+    idx = torch.arange(V, device=dev).expand_as(x)
+    T = temperature.to(dtype)
+    greedy = T == 0
+    top = x.max(-1, keepdim=True).values
+    greedy_tok = torch.where(x == top, idx, V).min(-1).values
+    # top-k on the stored values: ties at the k-th value are all kept
+    xs, order = x.sort(-1, descending=True)
+    k = top_k.to(torch.int64)
+    k_on = (k > 0) & (k < V)
+    kth = xs.gather(1, (k.clamp(1, V) - 1).unsqueeze(1))
+    keep = (x >= kth) | ~k_on.unsqueeze(1)
+    xt = x / torch.where(greedy, torch.ones_like(T), T).unsqueeze(1)
+    w = torch.where(keep, torch.exp(xt - xt.max(-1, keepdim=True).values), torch.zeros_like(x))
+    # top-p: a token stays iff the normalised mass of the kept tokens with a strictly
+    # larger logit is < p, so a class of equal logits stands or falls together
+    ws = w.gather(1, order)
+    before = ws.cumsum(-1) - ws  # mass in front of each sorted position
+    pos = torch.arange(V, device=dev).expand_as(x)
+    new_class = torch.ones_like(x, dtype=torch.bool)
+    new_class[:, 1:] = xs[:, 1:] != xs[:, :-1]
+    start = torch.where(new_class, pos, 0).cummax(-1).values  # first position of the class
+    above = before.gather(1, start)
+    keep_p = torch.zeros_like(keep).scatter(1, order, above / ws.sum(-1, keepdim=True)
+                                            < top_p.to(dtype).unsqueeze(1))
+    keep = keep & (keep_p | (x == top) | (top_p >= 1).unsqueeze(1))
+    w = torch.where(keep, w, torch.zeros_like(w))
+    # draw: the lowest kept index whose running sum, in index order, exceeds u * sum(w)
+    c = w.cumsum(-1)
+    hit = (c > u.to(dtype).unsqueeze(1) * w.sum(-1, keepdim=True)) & keep
+    first = torch.where(hit, idx, V).min(-1).values
+    last = torch.where(keep, idx, -1).max(-1).values
+    tok = torch.where(first < V, first, last)
+    return torch.where(greedy, greedy_tok, tok)
+
+
+def sample_logits(logits, temperature, top_k, top_p, seeds, steps, vocab_size=None):
+    """Per-row token sampling (ops/csrc/sample.hip semantics): the single definition.
+
+    ``logits`` [B, Vs], of which the first ``V = vocab_size or Vs`` columns count; per row
+    ``temperature`` fp32, ``top_k`` int32, ``top_p`` fp32, ``seeds`` int64, ``steps`` int32,
+    all [B]. Returns int64 [B]. Per row, with x the stored logits:
+
+    1. u = ``sample_uniform(seed, step)``.
+    2. temperature 0: the lowest index holding the row maximum.
+    3. top-k (off for k <= 0 or k >= V): keep {i : x_i >= k-th largest x}.
+    4. w_i = exp(x_i / T - max) over the kept set.
+    5. top-p (off for p >= 1): keep i iff the normalised mass of the kept tokens with
+       x_j > x_i is < p; the top value class always survives.
+    6. the token is the lowest kept index whose running sum of w in index order exceeds
+       u * sum(w), else the last kept index.
+
+    -inf logits are never chosen; NaN is out of contract."""
+    u = sample_uniform(seeds, steps)
+    return _sample_logits_u(logits, temperature, top_k, top_p, u, vocab_size)
+
+
 def _f(x):
     return x.to(torch.promote_types(x.dtype, torch.float32))
 

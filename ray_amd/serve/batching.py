@@ -27,11 +27,16 @@ class _Batcher:
         self.stream = inspect.isasyncgenfunction(fn)
         self.queue = None
         self.task = None
+        self.loop = None
 
     def _ensure(self):
-        if self.queue is None:
+        # the queue and the flush task belong to one event loop: a caller on another loop
+        # (the first one has ended, or an object with a recycled id()) gets fresh ones
+        loop = asyncio.get_running_loop()
+        if self.queue is None or self.loop is not loop:
+            self.loop = loop
             self.queue = asyncio.Queue()
-            self.task = asyncio.get_running_loop().create_task(self._loop())
+            self.task = loop.create_task(self._loop())
 
     async def _collect(self):
         first = await self.queue.get()

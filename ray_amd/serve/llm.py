@@ -8,8 +8,18 @@ Concurrent requests are collected by ``@serve.batch``, right-padded into ONE rag
 ``GPT2.generate`` call (KV cache, HIP decode attention on the GPU) that runs for the
 longest ``max_new_tokens`` of the batch, and every request gets its own tokens back, cut
 at its own ``max_new_tokens``. Greedy requests (temperature 0, the default) return what
-an un-batched ``generate`` returns; requests are grouped by temperature, because one
-``generate`` call samples at one temperature."""
+an un-batched ``generate`` returns.
+
+A request may carry its own ``temperature``, ``top_k``, ``top_p`` and ``seed``. A batch in
+which any request samples, or names ``top_p`` or ``seed``, is still ONE ``generate`` call:
+the device sampler (``rf.sample_logits``) takes every parameter per row, greedy requests
+ride along at temperature 0, and a request without ``seed`` gets the server's. The
+randomness of a token is a hash of the request's seed and the token's position, so a
+request's tokens are those of ``generate(..., seeds=[seed])`` on that request alone,
+whoever shared its batch. Every request is checked on its own before the call (empty
+prompt, a bad value, prompt + ``max_new_tokens`` past ``n_positions``), so a bad request
+is answered with an error and never fails its batch; a valid batch whose longest prompt
+plus longest ``max_new_tokens`` would not fit ``n_positions`` is split."""
 
 from __future__ import annotations
 
@@ -64,18 +74,85 @@ class GPT2Server:
                                   top_k=reqs[0].get("top_k"), generator=gen).cpu()
         return [out[b, : new[b]].tolist() for b in range(len(reqs))]
 
+    def _params(self, r):
+        """The request's checked (len, new, temperature, top_k, top_p, seed)."""
+        cfg = self.model.cfg
+        toks = r.get("tokens")
+        if not toks:
+            raise ValueError("request needs a non-empty 'tokens' list")
+        if any(not isinstance(t, int) or not 0 <= t < cfg.vocab_size for t in toks):
+            raise ValueError(f"tokens must be ints in [0, {cfg.vocab_size})")
+        new = int(r.get("max_new_tokens", 16))
+        if new < 1:
+            raise ValueError("max_new_tokens must be >= 1")
+        if len(toks) + new > cfg.n_positions:
+            raise ValueError(f"prompt ({len(toks)}) + max_new_tokens ({new}) exceeds "
+                             f"n_positions ({cfg.n_positions})")
+        temp = float(r.get("temperature", 0.0) or 0.0)
+        if not 0 <= temp < float("inf"):
+            raise ValueError("temperature must be >= 0")
+        top_k = r.get("top_k")
+        top_k = 0 if top_k is None else int(top_k)
+        top_p = r.get("top_p")
+        top_p = 1.0 if top_p is None else float(top_p)
+        if not 0 < top_p <= 1:
+            raise ValueError("top_p must be in (0, 1]")
+        seed = r.get("seed")
+        seed = self.seed if seed is None else int(seed)
+        if not -2 ** 63 <= seed < 2 ** 64:
+            raise ValueError("seed must fit 64 bits")
+        return len(toks), new, temp, top_k, top_p, seed
+
+    def _run_sampled(self, reqs, params):
+        """One ragged generate call through the device sampler, every parameter per row."""
+        lens = [p[0] for p in params]
+        new = [p[1] for p in params]
+        idx = torch.zeros(len(reqs), max(lens), dtype=torch.long)
+        for b, r in enumerate(reqs):
+            idx[b, : lens[b]] = torch.tensor(r["tokens"], dtype=torch.long)
+        out = self.model.generate(idx.to(self.device), max(new), lens=lens,
+                                  temperature=[p[2] for p in params],
+                                  top_k=[p[3] for p in params], top_p=[p[4] for p in params],
+                                  seeds=[p[5] for p in params]).cpu()
+        return [out[b, : new[b]].tolist() for b in range(len(reqs))]
+
     @batch(max_batch_size=8, batch_wait_timeout_s=0.01)
     async def _generate_batch(self, reqs):
         results = [None] * len(reqs)
-        groups = {}
+        params = {}
         for i, r in enumerate(reqs):
             try:
-                if not r.get("tokens"):
-                    raise ValueError("request needs a non-empty 'tokens' list")
-                key = (float(r.get("temperature", 0.0) or 0.0), r.get("top_k"))
-                groups.setdefault(key, []).append(i)
+                params[i] = self._params(r)
             except Exception as e:  # noqa: BLE001  (one bad request must not fail its batch)
                 results[i] = {"error": f"{type(e).__name__}: {e}"}
+        if any(p[2] > 0 or reqs[i].get("top_p") is not None or reqs[i].get("seed") is not None
+               for i, p in params.items()):
+            # one call, split only where the longest prompt and the longest continuation
+            # of the batch together would not fit the model's positions
+            chunks, cur = [], []
+            for i in params:
+                trial = cur + [i]
+                if cur and max(params[j][0] for j in trial) + max(params[j][1] for j in trial) \
+                        > self.model.cfg.n_positions:
+                    chunks.append(cur)
+                    trial = [i]
+                cur = trial
+            if cur:
+                chunks.append(cur)
+            for members in chunks:
+                try:
+                    got = self._run_sampled([reqs[i] for i in members],
+                                            [params[i] for i in members])
+                    for i, toks in zip(members, got):
+                        results[i] = {"tokens": toks}
+                except ValueError as e:
+                    for i in members:
+                        results[i] = {"error": f"ValueError: {e}"}
+            return results
+        # all greedy, none of the sampler's fields: the scalar path
+        groups = {}
+        for i in params:
+            groups.setdefault((0.0, reqs[i].get("top_k")), []).append(i)
         for members in groups.values():
             try:
                 for i, toks in zip(members, self._run([reqs[i] for i in members])):
