@@ -32,7 +32,7 @@
 //                   dV += P^T·dO and dK += dS^T·Q with P / dS as A operands. The
 //                   accumulators of S and dP start at -LSE/c and -delta (row constants
 //                   as the initial accumulator), so P = exp2(c·S'), dS = P·dP'.
-//   attn_bwd_dq   : one workgroup per 128 queries (forward orientation):
+//   attn_bwd_dq   : one workgroup per pair of 128-query blocks (forward orientation):
 //                   dQ^T += K^T·dS^T.
 // Softmax statistics are kept in the log2 domain (exp2 with scale·log2e folded).
 #include "common.h"
@@ -130,6 +130,21 @@ __device__ __forceinline__ int xcd_block(int bid, int n) {
   return (n & 7) ? bid : (bid & 7) * (n >> 3) + (bid >> 3);
 }
 
+// Paired causal blocks (forward and dQ): a workgroup takes query block nb-1-i (the heavy one,
+// most tiles) and then block i, so every workgroup sweeps the same nb+1 tile pairs and pays
+// one cold start for two blocks. An odd count leaves the middle block alone (nb = 1: the
+// only block). Logical ids are (b, h)-major, so xcd_block keeps a (b, h) on one XCD as before.
+struct PairedBlock {
+  int i, bh;
+  bool two;
+  __device__ __forceinline__ PairedBlock(int L, int nb) {
+    const int np = (nb + 1) / 2;
+    i = L % np;
+    bh = L / np;
+    two = nb - 1 - i != i;
+  }
+};
+
 // ---------------------------------------------------------------- tile staging
 // [64 rows][64] bf16 tile, global row stride `gstride` elements; 256 threads x 2 chunks
 // native vector type: HIP's uint4 is a struct, whose copies lower to memcpy through a
@@ -145,6 +160,14 @@ struct QD {
   TileRegs q, d;
   float rc;  // -lse/c (threads 0..63) or -delta (64..127) of the tile's rows
 };
+
+// member-wise (a struct assignment may lower to memcpy, see u32x4 above)
+__device__ __forceinline__ void kv_move(KV& d, const KV& s) {
+  d.k.v0 = s.k.v0;
+  d.k.v1 = s.k.v1;
+  d.v.v0 = s.v.v0;
+  d.v.v1 = s.v.v1;
+}
 
 __device__ __forceinline__ void tile_load(TileRegs& r, const bf16_t* g, long gstride) {
   const int c = threadIdx.x;
@@ -175,8 +198,54 @@ __device__ __forceinline__ void tile_store(const TileRegs& r, bf16_t* img) {
   *reinterpret_cast<u32x4*>(img + img_off((c + 256) >> 3, c & 7)) = r.v1;
 }
 
+// ---------------------------------------------------------------- epilogue staging
+// The forward's O and the dQ tiles leave through LDS: after a block's last tile barrier the
+// tile buffers are dead, so each wave re-lays its accumulators in a private region and stores
+// 16 bytes per lane, 8 whole 128-byte rows per instruction (stored directly, the
+// row-per-lane accumulator costs twice as many 8-byte stores, each touching 32 rows). The
+// regions are wave-private: LDS operations of one wave execute in order, so only the compiler
+// has to be kept from moving the reads above the writes — no workgroup barrier.
+__device__ __forceinline__ void wave_lds_order() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// The lane id again, opaque to the compiler. The epilogues of the paired-block loops derive
+// their lane-constant addresses from it, so that these are computed at the epilogue and not
+// hoisted out of the block loop, where they would stay live (and spill) through the tile loop.
+__device__ __forceinline__ int opaque_lane(int lane) {
+  asm volatile("" : "+v"(lane));
+  return lane;
+}
+
+// O^T / dQ^T accumulators (rows = d in registers, lane = one of the wave's 32 queries),
+// times `mul`, → 32 global rows of 128 bytes. `img`: 2048 elements, the swizzled [32][64]
+// image of tile_store (8-byte writes: 2-way conflicts; b128 row reads: conflict-free).
+// Each store instruction covers 8 whole rows.
+__device__ __forceinline__ void store_rows_lds(bf16_t* img, const f32x16 (&acc)[2], float mul,
+                                               bf16_t* g0, long gstride, int lane) {
+  const int r = lane & 31, hh = lane >> 5;
+#pragma unroll
+  for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      float v[4] = {acc[dt][4 * g] * mul, acc[dt][4 * g + 1] * mul, acc[dt][4 * g + 2] * mul,
+                    acc[dt][4 * g + 3] * mul};
+      *reinterpret_cast<uint2*>(img + img_off(r, 4 * dt + g) + 4 * hh) = pack4(v);
+    }
+  wave_lds_order();
+#pragma unroll
+  for (int s = 0; s < 4; ++s) {
+    const int row = 8 * s + (lane >> 3), ch = lane & 7;
+    *reinterpret_cast<u32x4*>(g0 + row * gstride + ch * 8) =
+        *reinterpret_cast<const u32x4*>(img + img_off(row, ch));
+  }
+}
+
 // ============================================================================ forward
-// One workgroup covers 128 queries: each wave owns 32 (QB = 1 block of 32), two waves per SIMD.
+// One workgroup covers a pair of 128-query blocks, one after the other (PairedBlock): each
+// wave owns 32 queries of the block (QB = 1 block of 32), two waves per SIMD.
 // (Measured and removed: two 32-query blocks per wave at one wave per SIMD, and a 3-waves-
 // per-SIMD register budget — profiles/r5/r5ao, r5at.)
 __global__ __launch_bounds__(256) void attn_fwd_kernel(const bf16_t* __restrict__ qkv,
@@ -188,33 +257,46 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const bf16_t* __restrict_
   constexpr int QW = 32 * QB;    // queries per wave
   constexpr int QBLK = 4 * QW;   // queries per workgroup
   const int nqb = T / QBLK;
-  const int L = xcd_block(blockIdx.x, gridDim.x);
-  const int qb = nqb - 1 - L % nqb;  // heaviest causal blocks first
-  const int bh = L / nqb;
+  const PairedBlock pb(xcd_block(blockIdx.x, gridDim.x), nqb);
+  const int bh = pb.bh;
   const int b = bh / H, h = bh % H;
   const int C = H * HD;
   const long tok = 3L * C;
   const bf16_t* base = qkv + (long)b * T * tok + h * HD;
   const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, r = lane & 31, hh = lane >> 5;
   const LaneOffs lo(lane);
-  const int q0 = qb * QBLK;
-  const int wave_qmin = q0 + QW * w;
-  const int wave_qmax = wave_qmin + QW - 1;
+  // per-block state: the heavy block nqb-1-i first, then (second pass) the light block i
+  int qb = nqb - 1 - pb.i;
+  int q0, wave_qmin, wave_qmax, ntiles;
   int qrow[QB];
   bf16x8_t qf[QB][4];
   f32x16 o[QB][2];
   float m_run[QB], l_run[QB];
+  auto set_block = [&]() __attribute__((always_inline)) {
+    q0 = qb * QBLK;
+    wave_qmin = q0 + QW * w;
+    wave_qmax = wave_qmin + QW - 1;
+    ntiles = (q0 + QBLK) / 64;
 #pragma unroll
-  for (int j = 0; j < QB; ++j) {
-    qrow[j] = wave_qmin + 32 * j + r;
+    for (int j = 0; j < QB; ++j) {
+      qrow[j] = wave_qmin + 32 * j + r;
+      o[j][0] = f32x16{};
+      o[j][1] = f32x16{};
+      m_run[j] = -INFINITY;
+      l_run[j] = 0.f;
+    }
+  };
+  // ln: the lane id (the seam passes opaque_lane, which pins the loads there)
+  auto load_q = [&](bf16x8_t (&x)[QB][4], int blk, int ln) __attribute__((always_inline)) {
 #pragma unroll
-    for (int kk = 0; kk < 4; ++kk) qf[j][kk] = ld8(base + (long)qrow[j] * tok + 16 * kk + 8 * hh);
-    o[j][0] = f32x16{};
-    o[j][1] = f32x16{};
-    m_run[j] = -INFINITY;
-    l_run[j] = 0.f;
-  }
-  const int ntiles = (q0 + QBLK) / 64;
+    for (int j = 0; j < QB; ++j)
+#pragma unroll
+      for (int kk = 0; kk < 4; ++kk)
+        x[j][kk] = ld8(base + (long)(blk * QBLK + QW * w + 32 * j + (ln & 31)) * tok + 16 * kk +
+                       8 * (ln >> 5));
+  };
+  set_block();
+  load_q(qf, qb, lane);
   KV A, B;
   const __amdgpu_buffer_rsrc_t rs =
       __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (T - 1) * (int)tok * 2 + 3 * C * 2,
@@ -316,26 +398,38 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const bf16_t* __restrict_
     __syncthreads();
   };
   load_kv(A, 0);
-  store_kv(A, 0);
-  load_kv(A, 1);  // ntiles >= 2
-  __syncthreads();
-  for (int t = 0; t < ntiles; t += 2) {
-    step(t, A, B);
-    if (t + 1 < ntiles) step(t + 1, B, A);
-  }
+  load_kv(B, 1);  // ntiles >= 2
+  for (bool more = pb.two;; more = false) {
+    store_kv(A, 0);
+    kv_move(A, B);
+    __syncthreads();
+    for (int t = 0; t < ntiles; t += 2) {
+      step(t, A, B);
+      if (t + 1 < ntiles) step(t + 1, B, A);
+    }
+    // The seam: the light block's Q fragments (qf is dead after the last tile) and its first
+    // two tiles are requested before the heavy block's epilogue, so no HBM round trip is
+    // exposed between the two.
+    if (more) {
+      load_q(qf, pb.i, opaque_lane(lane));
+      load_kv(A, 0);
+      load_kv(B, 1);
+    }
+    // The K/V images are dead after the last tile's barrier: O leaves through buffer 1. The
+    // next block writes buffer 0 first and buffer 1 only after its first barrier, by which
+    // every wave has read its staging region back.
+    static_assert(4 * QB * 2048 <= 2 * TILE_ELEMS, "O staging must fit one tile buffer");
 #pragma unroll
-  for (int j = 0; j < QB; ++j) {
-    const float inv = 1.f / l_run[j];
-    bf16_t* orow = out + ((long)b * T + qrow[j]) * C + h * HD;
-#pragma unroll
-    for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        float v[4] = {o[j][dt][4 * g] * inv, o[j][dt][4 * g + 1] * inv,
-                      o[j][dt][4 * g + 2] * inv, o[j][dt][4 * g + 3] * inv};
-        *reinterpret_cast<uint2*>(orow + 32 * dt + 8 * g + 4 * hh) = pack4(v);
-      }
-    if (hh == 0) lse[(long)bh * T + qrow[j]] = m_run[j] + log2f(l_run[j]);
+    for (int j = 0; j < QB; ++j) {
+      const float inv = 1.f / l_run[j];
+      store_rows_lds(lds + 2 * TILE_ELEMS + (w * QB + j) * 2048, o[j], inv,
+                     out + ((long)b * T + wave_qmin + 32 * j) * C + h * HD, C,
+                     opaque_lane(lane));
+      if (hh == 0) lse[(long)bh * T + qrow[j]] = m_run[j] + log2f(l_run[j]);
+    }
+    if (!more) break;
+    qb = pb.i;
+    set_block();
   }
 }
 
@@ -346,7 +440,10 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const bf16_t* __restrict_
 // chains of both halves issue first, then each half's softmax VALU runs while the other
 // half's MFMAs execute. (Measured and removed: a two-register-set prefetch, a fused pass that
 // also produced dQ through fp32 atomics, row constants read from global memory instead of
-// LDS — profiles/r2/attn_bwd_fused_vs_split.md, profiles/r5/r5aj, r5au.)
+// LDS — profiles/r2/attn_bwd_fused_vs_split.md, profiles/r5/r5aj, r5au; dK / dV staged
+// transposed in the dead Q/dO images and stored as 8 16-byte stores per lane instead of the
+// 64 two-byte ones below: +3.5 % kernel time; paired key blocks as in the forward / dQ: the
+// block loop spills in the tile loop at this kernel's 248 VGPRs — profiles/attn_block_cost.)
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void attn_bwd_dkdv_kernel(
     const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ dout,
     const float* __restrict__ lse, const float* __restrict__ delta, bf16_t* __restrict__ dqkv,
@@ -490,7 +587,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     }
 }
 
-// dQ: workgroup = 128 queries; forward orientation (S^T, lanes = queries); two K/V register
+// dQ: workgroup = a pair of 128-query blocks (PairedBlock), one after the other; forward
+// orientation (S^T, lanes = queries); two K/V register
 // sets (tile t+2 in flight). The kernel also computes delta = rowsum(dO * O) of its own
 // queries (each lane already holds half of its query's dO row; O is read the same way and
 // the halves meet by one permlane32 swap) and writes it for the dK/dV kernel that runs after
@@ -501,37 +599,56 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(
     int T, int H, float sc_log2, float scale, const bf16_t* __restrict__ out) {
   __shared__ __attribute__((aligned(16))) bf16_t lds[2 * 2 * TILE_ELEMS];  // [buf][K, V]
   const int nqb = T / 128;
-  const int L = xcd_block(blockIdx.x, gridDim.x);
-  const int qb = nqb - 1 - L % nqb;
-  const int bh = L / nqb;
+  const PairedBlock pb(xcd_block(blockIdx.x, gridDim.x), nqb);
+  const int bh = pb.bh;
   const int b = bh / H, h = bh % H;
   const int C = H * HD;
   const long tok = 3L * C;
   const bf16_t* base = qkv + (long)b * T * tok + h * HD;
   const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, r = lane & 31, hh = lane >> 5;
   const LaneOffs lo(lane);
-  const int q0 = qb * 128;
-  const int qrow = q0 + 32 * w + r;
+  // what a block needs from global memory before its first tile: this lane's Q / dO / O
+  // half rows and its query's LSE
+  struct RowIn {
+    bf16x8_t q[4], d[4], o[4];
+    float lse;
+  };
+  // ln: the lane id (the seam passes opaque_lane, which pins the loads there)
+  auto load_rows = [&](RowIn& x, int blk, int ln) __attribute__((always_inline)) {
+    const int row = blk * 128 + 32 * w + (ln & 31), c0 = 8 * (ln >> 5);
+#pragma unroll
+    for (int kk = 0; kk < 4; ++kk) {
+      x.q[kk] = ld8(base + (long)row * tok + 16 * kk + c0);
+      x.d[kk] = ld8(dout + ((long)b * T + row) * C + h * HD + 16 * kk + c0);
+      x.o[kk] = ld8(out + ((long)b * T + row) * C + h * HD + 16 * kk + c0);
+    }
+    x.lse = lse[(long)bh * T + row];
+  };
+  // per-block state: the heavy block nqb-1-i first, then (second pass) the light block i
+  int q0, qrow, ntiles, wave_qmax;
   bf16x8_t qf[4], df[4];
+  float nlq, ndel;
+  f32x16 dq[2];
+  auto set_block = [&](int blk, const RowIn& x) __attribute__((always_inline)) {
+    q0 = blk * 128;
+    qrow = q0 + 32 * w + r;
+    ntiles = (q0 + 128) / 64;
+    wave_qmax = q0 + 32 * w + 31;
+    nlq = -x.lse / sc_log2;
+    float part = 0.f;
 #pragma unroll
-  for (int kk = 0; kk < 4; ++kk) {
-    qf[kk] = ld8(base + (long)qrow * tok + 16 * kk + 8 * hh);
-    df[kk] = ld8(dout + ((long)b * T + qrow) * C + h * HD + 16 * kk + 8 * hh);
-  }
-  const float nlq = -lse[(long)bh * T + qrow] / sc_log2;
-  float part = 0.f;
+    for (int kk = 0; kk < 4; ++kk) {
+      qf[kk] = x.q[kk];
+      df[kk] = x.d[kk];
 #pragma unroll
-  for (int kk = 0; kk < 4; ++kk) {
-    const bf16x8_t of = ld8(out + ((long)b * T + qrow) * C + h * HD + 16 * kk + 8 * hh);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) part += (float)of[j] * (float)df[kk][j];
-  }
-  const float dl = half_sum(part);
-  if (hh == 0) delta[(long)bh * T + qrow] = dl;
-  const float ndel = -dl;
-  f32x16 dq[2] = {};
-  const int ntiles = (q0 + 128) / 64;
-  const int wave_qmax = q0 + 32 * w + 31;
+      for (int j = 0; j < 8; ++j) part += (float)x.o[kk][j] * (float)x.d[kk][j];
+    }
+    const float dl = half_sum(part);
+    if (hh == 0) delta[(long)bh * T + qrow] = dl;
+    ndel = -dl;
+    dq[0] = f32x16{};
+    dq[1] = f32x16{};
+  };
   KV A, B;
   const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
       (void*)base, 0, (T - 1) * (int)tok * 2 + 3 * C * 2, 0x00020000);
@@ -592,32 +709,46 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(
     if (t + 1 < ntiles) store_kv(held, t + 1);
     __syncthreads();
   };
-  load_kv(A, 0);
-  store_kv(A, 0);
-  load_kv(A, 1);  // ntiles >= 2
-  __syncthreads();
-  for (int t = 0; t < ntiles; t += 2) {
-    step(t, A, B);
-    if (t + 1 < ntiles) step(t + 1, B, A);
+  {
+    RowIn x;
+    load_rows(x, nqb - 1 - pb.i, lane);
+    load_kv(A, 0);
+    load_kv(B, 1);  // ntiles >= 2
+    set_block(nqb - 1 - pb.i, x);
   }
-  bf16_t* g = dqkv + ((long)b * T + qrow) * tok + h * HD;
-#pragma unroll
-  for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-    for (int gi = 0; gi < 4; ++gi) {
-      float v[4] = {dq[dt][4 * gi] * scale, dq[dt][4 * gi + 1] * scale,
-                    dq[dt][4 * gi + 2] * scale, dq[dt][4 * gi + 3] * scale};
-      *reinterpret_cast<uint2*>(g + 32 * dt + 8 * gi + 4 * hh) = pack4(v);
+  for (bool more = pb.two;; more = false) {
+    store_kv(A, 0);
+    kv_move(A, B);
+    __syncthreads();
+    for (int t = 0; t < ntiles; t += 2) {
+      step(t, A, B);
+      if (t + 1 < ntiles) step(t + 1, B, A);
     }
+    // The seam (as in the forward): the light block's rows and first two tiles are requested
+    // before the heavy block's epilogue. dQ leaves through buffer 1, which the next block
+    // writes only after its first barrier.
+    RowIn x;
+    if (more) {
+      load_rows(x, pb.i, opaque_lane(lane));
+      load_kv(A, 0);
+      load_kv(B, 1);
+    }
+    store_rows_lds(lds + 2 * TILE_ELEMS + w * 2048, dq, scale,
+                   dqkv + ((long)b * T + q0 + 32 * w) * tok + h * HD, tok, opaque_lane(lane));
+    if (!more) break;
+    set_block(pb.i, x);
+  }
 }
 
 static inline bool attn_shape_ok(int T, int D) { return D == HD && T % 128 == 0 && T >= 128; }
+// one workgroup per pair of 128-row blocks (PairedBlock)
+static inline int attn_grid(int B, int T, int H) { return B * H * ((T / 128 + 1) / 2); }
 
 RA_EXPORT int ra_attn_fwd(const void* qkv, void* out, float* lse, int B, int T, int H, int D,
                           float scale, hipStream_t st) {
   if (!attn_shape_ok(T, D)) return hipErrorInvalidValue;
   const float sc_log2 = scale * 1.4426950408889634f;
-  hipLaunchKernelGGL(attn_fwd_kernel, dim3(B * H * (T / 128)), dim3(256), 0, st,
+  hipLaunchKernelGGL(attn_fwd_kernel, dim3(attn_grid(B, T, H)), dim3(256), 0, st,
                      (const bf16_t*)qkv, (bf16_t*)out, lse, T, H, sc_log2);
   return hipGetLastError();
 }
@@ -628,7 +759,7 @@ RA_EXPORT int ra_attn_bwd(const void* qkv, const void* out, const void* dout, co
                           hipStream_t st) {
   if (!attn_shape_ok(T, D)) return hipErrorInvalidValue;
   const float sc_log2 = scale * 1.4426950408889634f;
-  hipLaunchKernelGGL(attn_bwd_dq_kernel, dim3(B * H * (T / 128)), dim3(256), 0, st,
+  hipLaunchKernelGGL(attn_bwd_dq_kernel, dim3(attn_grid(B, T, H)), dim3(256), 0, st,
                      (const bf16_t*)qkv, (const bf16_t*)dout, lse, delta, (bf16_t*)dqkv, T, H,
                      sc_log2, scale, (const bf16_t*)out);
   hipLaunchKernelGGL(attn_bwd_dkdv_kernel, dim3(B * H * (T / 128)), dim3(256), 0, st,
