@@ -27,7 +27,9 @@ MI355X-first choices:
   row lengths kept on the device: no host sync, one HIP-graph capture serves every
   position); ``generate`` drives them. With ``seeds=`` the next token comes from the HIP
   sampler (ops/csrc/sample.hip: temperature, top-k, top-p and seed per row, one launch, no
-  host sync) and the whole step, sampler included, is one graph replay.
+  host sync) and the whole step, sampler included, is one graph replay. ``prefill_into``
+  writes a prefill's K/V into device-chosen rows of a wider cache (ops/csrc/kv_slots.hip):
+  the admission path of the continuous-batching engine, models/gpt2_engine.py.
 """
 
 from __future__ import annotations
@@ -299,24 +301,59 @@ class GPT2(nn.Module):
         each row's last real token, [B, vocab_size]. Causal attention keeps the padding
         out of the real positions; the padded positions' K/V are leftovers that the decode
         kernel masks out and overwrites."""
-        cfg = self.cfg
         B, T = idx.shape
-        H, hd = cfg.n_head, cfg.n_embd // cfg.n_head
         if B != cache.k.shape[1]:
             raise ValueError(f"cache holds {cache.k.shape[1]} rows, prompts have {B}")
         lens = torch.as_tensor(lens, device=idx.device).to(torch.int32)
+        n = min(T, cache.max_len)
+
+        def store(i, qkv):
+            cache.k[i, :, :, :n].copy_(qkv[:, :n, 1].transpose(1, 2))
+            cache.v[i, :, :, :n].copy_(qkv[:, :n, 2].transpose(1, 2))
+
+        logits = self._prefill(idx, lens, store)
+        cache.lens = lens.clone()
+        return logits
+
+    @torch.no_grad()
+    def prefill_into(self, idx, lens, cache: KVCache, slots):
+        """``prefill`` into rows of a cache that is wider than the prompts' batch: row b of
+        ``idx`` [Bn, T] (true lengths ``lens`` [Bn], >= 1) goes to row ``slots[b]`` of
+        ``cache`` (``slots`` int32 [Bn] on the device, distinct), through ``rf.kv_insert``:
+        only positions below ``lens[b]`` of the named rows are written, the other rows and
+        the padding keep their bytes. Writes ``cache.lens`` IN PLACE at ``slots`` (a
+        captured step holds its address) and returns the logits of each row's last real
+        token, [Bn, vocab_size]."""
+        if not isinstance(slots, torch.Tensor) or slots.dtype != torch.int32 or \
+                slots.shape != (idx.shape[0],) or slots.device != idx.device:
+            raise ValueError(f"slots must be an int32 tensor of shape [{idx.shape[0]}] on "
+                             f"{idx.device}")
+        lens = torch.as_tensor(lens, device=idx.device).to(torch.int32)
+        logits = self._prefill(
+            idx, lens, lambda i, qkv: rf.kv_insert(qkv, cache.k[i], cache.v[i], slots, lens))
+        # a slot id outside the cache lands in a spare entry, as kv_insert skips it
+        S = cache.lens.shape[0]
+        sl = slots.long()
+        sl = torch.where((sl >= 0) & (sl < S), sl, S)
+        cache.lens.copy_(torch.cat([cache.lens, cache.lens.new_zeros(1)]).scatter_(0, sl, lens)[:S])
+        return logits
+
+    def _prefill(self, idx, lens, store):
+        """The prompt pass of ``prefill`` / ``prefill_into``: ``store(i, qkv)`` takes layer
+        i's packed c_attn output [B, Tp, 3, H, hd] (Tp >= T: the padded width)."""
+        cfg = self.cfg
+        B, T = idx.shape
+        H, hd = cfg.n_head, cfg.n_embd // cfg.n_head
         Tp = T
         if self._flash_ok(self.wte) and T % 128 and -(-T // 128) * 128 <= cfg.n_positions:
             # the MFMA flash kernel wants T % 128 == 0; more right padding is as harmless
             Tp = -(-T // 128) * 128
             idx = F.pad(idx, (0, Tp - T))
-        n = min(T, cache.max_len)
         x = rf.embedding(idx, self.wte, self.wpe)
         x, h = self.h[0].ln_1.fork(x)
         for i, blk in enumerate(self.h):
             qkv = F.linear(h, blk.c_attn_w, blk.c_attn_b).view(B, Tp, 3, H, hd)
-            cache.k[i, :, :, :n].copy_(qkv[:, :n, 1].transpose(1, 2))
-            cache.v[i, :, :, :n].copy_(qkv[:, :n, 2].transpose(1, 2))
+            store(i, qkv)
             y = rf.causal_attention_qkv(qkv)
             a = F.linear(y.reshape(B, Tp, cfg.n_embd), blk.c_proj_w)
             x, h = rf.residual_layer_norm(a, blk.c_proj_b, x, blk.ln_2.weight, blk.ln_2.bias,
@@ -327,7 +364,6 @@ class GPT2(nn.Module):
         # only the last real position of each row meets the LM head: [B, C] x [C, V]
         last = (lens.long() - 1).clamp(0, Tp - 1)
         hl = h[torch.arange(B, device=idx.device), last]
-        cache.lens = lens.clone()
         return F.linear(hl, self.wte)[:, : cfg.vocab_size]
 
     @torch.no_grad()

@@ -1,0 +1,258 @@
+"""Continuous batching for GPT-2 generation: a persistent KV cache of S slots that requests
+enter and leave independently, between replays of ONE captured decode step.
+
+    eng = GPT2Engine(model, slots=8)
+    rid = eng.submit([464, 3290], 32, temperature=0.8, seed=7)
+    while eng.has_work():
+        for rid, new_tokens, finished in eng.step():
+            ...
+
+The device step is the one of ``generate(seeds=...)`` (``rf.sample_logits`` with the per-slot
+parameters and ``cache.lens`` as the hash step, then ``decode_step`` back into the fixed
+logits buffer) with the engine's bookkeeping, ``rf.slot_advance``, between the two: it
+stores the token, counts it, retires the slot at ``max_new_tokens`` or EOS, and pins the
+``cache.lens`` of every idle slot to ``SLOT_INACTIVE``, which the decode-attention kernel
+treats as an inactive row (no cache write, zero output). The step has a fixed width S and
+touches nothing on the host, so it is captured once and every later step is one replay.
+
+Admission runs between replays: one ragged ``GPT2.prefill_into`` for all the prompts that
+found a free slot (``rf.kv_insert`` moves their K/V into the slots' rows), then the
+per-slot parameters and the prefill's logits rows go into the fixed buffers. A request's
+tokens are those of ``model.generate(prompt, max_new_tokens, ..., seeds=[seed])`` on that
+request alone, cut after the first EOS: whenever it was admitted, in whichever slot, and
+whoever shared the step.
+
+``poll_every``: device steps per ``step()`` call, between two polls. A poll is one download
+and a host synchronisation, during which the GPU idles; at 8 (the default) the engine beat
+static batching at both measured widths, at 1 only at S = 8 (profiles/r10/engine.md). The
+price: tokens arrive in groups of up to ``poll_every``, and a slot that finishes inside a
+group stays idle until the group ends.
+
+Single-threaded by contract: every call comes from one thread."""
+
+from __future__ import annotations
+
+import collections
+import math
+
+import torch
+
+from ray_amd.models.gpt2 import GPT2, KVCache
+from ray_amd.ops import functional as rf
+
+
+class _Request:
+    __slots__ = ("rid", "tokens", "max_new", "temperature", "top_k", "top_p", "seed")
+
+    def __init__(self, rid, tokens, max_new, temperature, top_k, top_p, seed):
+        self.rid, self.tokens, self.max_new = rid, tokens, max_new
+        self.temperature, self.top_k, self.top_p, self.seed = temperature, top_k, top_p, seed
+
+
+class GPT2Engine:
+    def __init__(self, model: GPT2, slots=8, max_len=None, eos_token_id=None, graph=None,
+                 poll_every=8):
+        cfg = model.cfg
+        dev = model.wte.device
+        S = int(slots)
+        if S < 1:
+            raise ValueError("slots must be >= 1")
+        if int(poll_every) < 1:
+            raise ValueError("poll_every must be >= 1")
+        if graph is None:
+            graph = dev.type == "cuda"
+        if graph and dev.type != "cuda":
+            raise ValueError("graph=True needs the model on the GPU")
+        self.model, self.slots, self.device = model, S, dev
+        self.max_len = cfg.n_positions if max_len is None else int(max_len)
+        self.eos = None if eos_token_id is None else int(eos_token_id)
+        self.poll_every = int(poll_every)
+        self.steps = 0  # device steps so far
+
+        # everything the captured step reads or writes: allocated once, fixed addresses
+        self.cache = KVCache(cfg, S, self.max_len, dev, model.wte.dtype)
+        self.cache.lens.fill_(rf.SLOT_INACTIVE)
+        self.buf = torch.zeros(S, cfg.padded_vocab, device=dev, dtype=model.wte.dtype)
+        self.logits = self.buf[:, : cfg.vocab_size]
+        self.temperature = torch.zeros(S, dtype=torch.float32, device=dev)
+        self.top_k = torch.zeros(S, dtype=torch.int32, device=dev)
+        self.top_p = torch.ones(S, dtype=torch.float32, device=dev)
+        self.seeds = torch.zeros(S, dtype=torch.int64, device=dev)
+        self.n_out = torch.zeros(S, dtype=torch.int32, device=dev)
+        self.max_new = torch.zeros(S, dtype=torch.int32, device=dev)
+        self.active = torch.zeros(S, dtype=torch.uint8, device=dev)
+        self.out = torch.zeros(S, self.max_len, dtype=torch.int64, device=dev)
+        self._seen = torch.zeros(S, dtype=torch.int64, device=dev)  # n_out at the last poll
+        self._ar = torch.arange(self.poll_every, device=dev).unsqueeze(0)
+
+        self._queue = collections.deque()
+        self._slot_req = [None] * S  # the request running in each slot
+        self._seen_host = [0] * S
+        self._next_rid = 0
+        self._graph = None
+        if graph:
+            from ray_amd.ops.graph_lock import CAPTURE_LOCK
+
+            with torch.no_grad():
+                self._device_step()  # every slot idle: warms up what the capture needs
+            torch.cuda.synchronize(dev)
+            self._graph = torch.cuda.CUDAGraph()
+            with CAPTURE_LOCK, torch.no_grad(), torch.cuda.graph(self._graph):
+                self._device_step()
+
+    # ------------------------------------------------------------------ the device step
+    def _device_step(self):
+        tok = rf.sample_logits(self.logits, self.temperature, self.top_k, self.top_p, self.seeds,
+                               self.cache.lens, validate=False)
+        rf.slot_advance(tok, self.cache.lens, self.n_out, self.max_new, self.active, self.out,
+                        self.eos)
+        self.model.decode_step(tok, self.cache, out=self.buf)
+
+    def _run_step(self):
+        if self._graph is None:
+            with torch.no_grad():
+                self._device_step()
+        else:
+            from ray_amd.ops.graph_lock import CAPTURE_LOCK
+
+            with CAPTURE_LOCK:
+                self._graph.replay()
+        self.steps += 1
+
+    # ------------------------------------------------------------------ requests
+    def submit(self, tokens, max_new_tokens, temperature=0.0, top_k=None, top_p=None, seed=0):
+        """Queues a request and returns its id; a bad request raises ``ValueError`` and
+        queues nothing."""
+        cfg = self.model.cfg
+        if isinstance(tokens, torch.Tensor):
+            tokens = tokens.tolist()
+        tokens = list(tokens)
+        if not tokens:
+            raise ValueError("a request needs a non-empty prompt")
+        if any(isinstance(t, bool) or not isinstance(t, int) or not 0 <= t < cfg.vocab_size
+               for t in tokens):
+            raise ValueError(f"tokens must be ints in [0, {cfg.vocab_size})")
+        max_new = int(max_new_tokens)
+        if max_new < 1:
+            raise ValueError("max_new_tokens must be >= 1")
+        if len(tokens) + max_new > self.max_len:
+            raise ValueError(f"prompt ({len(tokens)}) + max_new_tokens ({max_new}) exceeds "
+                             f"max_len ({self.max_len})")
+        temperature = float(temperature)
+        if not (math.isfinite(temperature) and temperature >= 0):
+            raise ValueError("temperature must be finite and >= 0")
+        top_k = 0 if top_k is None else int(top_k)
+        top_p = 1.0 if top_p is None else float(top_p)
+        if not 0 < top_p <= 1:
+            raise ValueError("top_p must be in (0, 1]")
+        seed = int(seed)
+        if not -2 ** 63 <= seed < 2 ** 64:
+            raise ValueError("seed must fit 64 bits")
+        if seed >= 2 ** 63:
+            seed -= 2 ** 64
+        top_k = max(0, min(top_k, 2 ** 31 - 1))
+        rid = self._next_rid
+        self._next_rid += 1
+        self._queue.append(_Request(rid, tokens, max_new, temperature, top_k, top_p, seed))
+        return rid
+
+    def cancel(self, rid):
+        """Drops a queued or running request (its slot is free for the next admission); no
+        event follows for it. Returns whether the request was found."""
+        for r in self._queue:
+            if r.rid == rid:
+                self._queue.remove(r)
+                return True
+        for s, r in enumerate(self._slot_req):
+            if r is not None and r.rid == rid:
+                self.active[s] = 0
+                self.cache.lens[s] = rf.SLOT_INACTIVE
+                self._slot_req[s] = None
+                return True
+        return False
+
+    def has_work(self):
+        return bool(self._queue) or self.num_active > 0
+
+    @property
+    def num_active(self):
+        return sum(r is not None for r in self._slot_req)
+
+    @property
+    def num_queued(self):
+        return len(self._queue)
+
+    # ------------------------------------------------------------------ admission
+    def _admit(self):
+        free = [s for s, r in enumerate(self._slot_req) if r is None]
+        reqs = []
+        while self._queue and len(reqs) < len(free):
+            reqs.append(self._queue.popleft())
+        if not reqs:
+            return
+        dev = self.device
+        slots = free[: len(reqs)]
+        lens = [len(r.tokens) for r in reqs]
+        idx = torch.zeros(len(reqs), max(lens), dtype=torch.long)
+        for b, r in enumerate(reqs):
+            idx[b, : lens[b]] = torch.tensor(r.tokens, dtype=torch.long)
+        # three uploads per round, however many requests it admits
+        ints = torch.tensor([[s, n, r.top_k, r.max_new, r.seed]
+                             for s, n, r in zip(slots, lens, reqs)], dtype=torch.int64).to(dev)
+        flts = torch.tensor([[r.temperature, r.top_p] for r in reqs],
+                            dtype=torch.float32).to(dev)
+        sl = ints[:, 0]
+        logits = self.model.prefill_into(idx.to(dev), ints[:, 1].to(torch.int32), self.cache,
+                                         sl.to(torch.int32))
+        self.logits.index_copy_(0, sl, logits)
+        self.top_k.index_copy_(0, sl, ints[:, 2].to(torch.int32))
+        self.max_new.index_copy_(0, sl, ints[:, 3].to(torch.int32))
+        self.seeds.index_copy_(0, sl, ints[:, 4])
+        self.temperature.index_copy_(0, sl, flts[:, 0])
+        self.top_p.index_copy_(0, sl, flts[:, 1])
+        self.n_out.index_fill_(0, sl, 0)
+        self._seen.index_fill_(0, sl, 0)
+        self.active.index_fill_(0, sl, 1)
+        for s, r in zip(slots, reqs):
+            self._slot_req[s] = r
+            self._seen_host[s] = 0
+
+    # ------------------------------------------------------------------ poll
+    def _poll(self):
+        """One download, whatever S: per slot n_out, active and the (at most poll_every)
+        tokens it produced since the last poll."""
+        col = (self._seen.unsqueeze(1) + self._ar).clamp_(max=self.max_len - 1)
+        host = torch.cat([self.n_out.long().unsqueeze(1), self.active.long().unsqueeze(1),
+                          self.out.gather(1, col)], 1).tolist()
+        self._seen.copy_(self.n_out)
+        events = []
+        for s, r in enumerate(self._slot_req):
+            if r is None:
+                continue
+            n, act = host[s][0], host[s][1]
+            new = host[s][2: 2 + n - self._seen_host[s]]
+            self._seen_host[s] = n
+            if not act:
+                self._slot_req[s] = None
+            if new or not act:
+                events.append((r.rid, new, not act))
+        return events
+
+    def step(self):
+        """Admits queued requests into free slots, runs ``poll_every`` device steps and
+        polls: ``[(rid, new_tokens, finished), ...]`` for the slots that produced tokens."""
+        self._admit()
+        if self.num_active == 0:
+            return []
+        for _ in range(self.poll_every):
+            self._run_step()
+        return self._poll()
+
+    def run(self):
+        """Drives the engine until it is idle: ``{rid: tokens}`` of the requests that
+        produced tokens on the way."""
+        got = {}
+        while self.has_work():
+            for rid, new, _ in self.step():
+                got.setdefault(rid, []).extend(new)
+        return got

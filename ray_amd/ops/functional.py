@@ -645,6 +645,81 @@ def attn_decode(qkv_new, k_cache, v_cache, lens, scale=None, splits=None):
     return out
 
 
+SLOT_INACTIVE = ref.SLOT_INACTIVE  # cache.lens of an idle slot (ops/csrc/kv_slots.hip)
+
+
+def _int_vec(name, op, t, n, like, dtype=torch.int32):
+    if not isinstance(t, torch.Tensor) or t.shape != (n,) or t.dtype != dtype or \
+            t.device != like.device:
+        raise ValueError(f"{op}: {name} must be a {dtype} tensor of shape [{n}] on {like.device}")
+
+
+def kv_insert(qkv, k_cache, v_cache, slots, lens):
+    """Moves one layer's prefill K/V (``qkv`` [Bn, Tp, 3, H, D], the packed c_attn output
+    of the right-padded prompts) into slots of a wider cache: for every row b with
+    0 <= slots[b] < S, ``k_cache[slots[b], h, t] = qkv[b, t, 1, h]`` (V: index 2) for t in
+    [0, min(lens[b], Tp, Tmax)), IN PLACE in the caches [S, H, Tmax, D]; nothing else is
+    written. ``slots`` and ``lens`` (int32 [Bn], on the tensors' device) are only read, on
+    the device, and bounds-checked there: the call is graph-capturable, a bad slot or
+    length skips the work. Two rows naming one slot are the caller's error.
+
+    HIP kernel for bf16, D == 64 GPU tensors; CPU tensors, other dtypes and other head
+    sizes use the plain-torch reference."""
+    if qkv.dim() != 5 or qkv.shape[2] != 3:
+        raise ValueError(f"kv_insert: qkv must be [Bn, Tp, 3, H, D], got {tuple(qkv.shape)}")
+    Bn, Tp, _, H, D = qkv.shape
+    if k_cache.shape != v_cache.shape or k_cache.dim() != 4 or k_cache.shape[1] != H or \
+            k_cache.shape[3] != D:
+        raise ValueError("kv_insert: the caches must be [S, H, Tmax, D]")
+    S, _, Tmax, _ = k_cache.shape
+    if min(Bn, Tp, H, S, Tmax) < 1:
+        raise ValueError("kv_insert: empty qkv or cache")
+    if k_cache.dtype != v_cache.dtype or k_cache.device != qkv.device or \
+            v_cache.device != qkv.device:
+        raise ValueError("kv_insert: qkv and the caches must share a device, the caches a dtype")
+    _int_vec("slots", "kv_insert", slots, Bn, qkv)
+    _int_vec("lens", "kv_insert", lens, Bn, qkv)
+    if not (_hip(qkv) and qkv.dtype == torch.bfloat16 and D == 64
+            and k_cache.dtype == torch.bfloat16):
+        return ref.kv_insert(qkv, k_cache, v_cache, slots, lens)
+    if not (k_cache.is_contiguous() and v_cache.is_contiguous()):
+        raise ValueError("kv_insert: the caches are written in place and must be contiguous")
+    qkv = qkv.contiguous()
+    check(_lib.lib().ra_kv_insert(ptr(qkv), ptr(k_cache), ptr(v_cache), ptr(slots.contiguous()),
+                                  ptr(lens.contiguous()), Bn, Tp, H, S, Tmax, stream_ptr()),
+          "kv_insert")
+
+
+def slot_advance(tok, lens, n_out, max_new, active, out, eos_token_id=None):
+    """The continuous-batching engine's bookkeeping after the sampler, one launch, IN
+    PLACE: an active slot with ``n_out[s] < cap`` stores ``out[s, n_out[s]] = tok[s]``,
+    adds 1 to ``n_out[s]`` and becomes inactive if ``n_out[s] >= max_new[s]`` or the token
+    is ``eos_token_id``; an active slot with ``n_out[s] >= cap`` becomes inactive without
+    a write; every slot that is inactive after that gets ``lens[s] = SLOT_INACTIVE``, on
+    every call. ``tok`` int64 [S], ``lens`` / ``n_out`` / ``max_new`` int32 [S], ``active``
+    uint8 [S], ``out`` int64 [S, cap], on one device. No host sync: capturable.
+
+    HIP kernel for GPU tensors, the plain-torch reference otherwise."""
+    if tok.dim() != 1 or tok.dtype != torch.int64 or tok.shape[0] < 1:
+        raise ValueError("slot_advance: tok must be an int64 tensor of shape [S]")
+    S = tok.shape[0]
+    for name, t in (("lens", lens), ("n_out", n_out), ("max_new", max_new)):
+        _int_vec(name, "slot_advance", t, S, tok)
+    _int_vec("active", "slot_advance", active, S, tok, torch.uint8)
+    if not isinstance(out, torch.Tensor) or out.dim() != 2 or out.shape[0] != S or \
+            out.shape[1] < 1 or out.dtype != torch.int64 or out.device != tok.device:
+        raise ValueError(f"slot_advance: out must be an int64 tensor [{S}, cap] on {tok.device}")
+    eos = -1 if eos_token_id is None else int(eos_token_id)
+    if not _hip(tok):
+        return ref.slot_advance(tok, lens, n_out, max_new, active, out, eos)
+    for name, t in (("lens", lens), ("n_out", n_out), ("active", active), ("out", out)):
+        if not t.is_contiguous():
+            raise ValueError(f"slot_advance: {name} is written in place and must be contiguous")
+    check(_lib.lib().ra_slot_advance(ptr(tok.contiguous()), ptr(lens), ptr(n_out),
+                                     ptr(max_new.contiguous()), ptr(active), ptr(out), S,
+                                     out.shape[1], eos, stream_ptr()), "slot_advance")
+
+
 SAMPLE_MAX_VOCAB = 1 << 18  # ops/csrc/sample.hip kMaxV (checked against the library)
 
 

@@ -67,6 +67,61 @@ def attn_decode(qkv_new, k_cache, v_cache, lens, scale=None):
     return (p.unsqueeze(2) @ vf).squeeze(2).to(qkv_new.dtype)
 
 
+SLOT_INACTIVE = -(1 << 30)  # ops/csrc/kv_slots.hip kSlotInactive: an idle slot's cache.lens
+
+
+def kv_insert(qkv, k_cache, v_cache, slots, lens):
+    """Moves a prefill's K/V into slots of a wider cache (ops/csrc/kv_slots.hip semantics).
+
+    ``qkv`` [Bn, Tp, 3, H, D] is one layer's packed c_attn output for the right-padded
+    prompts, the caches are [S, H, Tmax, D], ``slots`` and ``lens`` integer [Bn]. For every
+    row b with 0 <= slots[b] < S, t in [0, min(lens[b], Tp, Tmax)) and every h,
+    ``k_cache[slots[b], h, t] = qkv[b, t, 1, h]`` and the same for V with index 2, IN PLACE;
+    every other element keeps its bits. Two rows naming one slot are the caller's error.
+    No host sync."""
+    Bn, Tp, _, H, D = qkv.shape
+    S, Tmax = k_cache.shape[0], k_cache.shape[2]
+    dev = qkv.device
+    n = min(Tp, Tmax)
+    slots = slots.long()
+    valid = (slots >= 0) & (slots < S)
+    # which prompt row feeds each slot (Bn: none); skipped rows land in a spare entry
+    row = torch.full((S + 1,), Bn, dtype=torch.long, device=dev)
+    row.scatter_(0, torch.where(valid, slots, S), torch.arange(Bn, device=dev))
+    row = row[:S]
+    fed = row < Bn
+    row = row.clamp(max=Bn - 1)
+    t = torch.arange(n, device=dev)
+    take = (fed.view(S, 1) & (t.view(1, n) < lens.long()[row].view(S, 1))).view(S, 1, n, 1)
+    for cache, which in ((k_cache, 1), (v_cache, 2)):
+        new = qkv[row, :n, which].transpose(1, 2).to(cache.dtype)  # [S, H, n, D]
+        cache[:, :, :n] = torch.where(take, new, cache[:, :, :n])
+
+
+def slot_advance(tok, lens, n_out, max_new, active, out, eos_token_id=None):
+    """The continuous-batching engine's bookkeeping after the sampler
+    (ops/csrc/kv_slots.hip semantics), everything IN PLACE: ``tok`` int64 [S], ``lens``,
+    ``n_out``, ``max_new`` int32 [S], ``active`` uint8 [S], ``out`` int64 [S, cap].
+
+    An active slot with 0 <= n_out[s] < cap stores ``out[s, n_out[s]] = tok[s]``, adds 1
+    to ``n_out[s]`` and becomes inactive if ``n_out[s] >= max_new[s]`` or ``tok[s]`` is
+    ``eos_token_id``; an active slot with any other ``n_out[s]`` becomes inactive without
+    a write. Every slot that is inactive after that gets ``lens[s] = SLOT_INACTIVE``.
+    No host sync."""
+    cap = out.shape[1]
+    n = n_out.long()
+    ok = active.bool() & (n >= 0) & (n < cap)
+    col = n.clamp(0, cap - 1).unsqueeze(1)
+    out.scatter_(1, col, torch.where(ok.unsqueeze(1), tok.unsqueeze(1), out.gather(1, col)))
+    n = n + ok
+    n_out.copy_(n)
+    stay = ok & (n < max_new)
+    if eos_token_id is not None and int(eos_token_id) >= 0:
+        stay = stay & (tok != int(eos_token_id))
+    active.copy_(stay)
+    lens.masked_fill_(~stay, SLOT_INACTIVE)
+
+
 _MASK64 = (1 << 64) - 1
 
 

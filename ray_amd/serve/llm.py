@@ -19,7 +19,13 @@ request's tokens are those of ``generate(..., seeds=[seed])`` on that request al
 whoever shared its batch. Every request is checked on its own before the call (empty
 prompt, a bad value, prompt + ``max_new_tokens`` past ``n_positions``), so a bad request
 is answered with an error and never fails its batch; a valid batch whose longest prompt
-plus longest ``max_new_tokens`` would not fit ``n_positions`` is split."""
+plus longest ``max_new_tokens`` would not fit ``n_positions`` is split.
+
+``build_gpt2_app(..., continuous=True, slots=S)`` binds ``GPT2EngineServer`` instead:
+continuous batching over S KV-cache slots (``models/gpt2_engine.py``). Requests enter and
+leave between replays of one captured decode step, so a 5-token request does not wait for
+a 900-token one, and ``handle.options(method_name="stream", stream=True)`` streams the
+tokens as they are produced. The same request fields and the same per-request guarantee."""
 
 from __future__ import annotations
 
@@ -76,32 +82,7 @@ class GPT2Server:
 
     def _params(self, r):
         """The request's checked (len, new, temperature, top_k, top_p, seed)."""
-        cfg = self.model.cfg
-        toks = r.get("tokens")
-        if not toks:
-            raise ValueError("request needs a non-empty 'tokens' list")
-        if any(not isinstance(t, int) or not 0 <= t < cfg.vocab_size for t in toks):
-            raise ValueError(f"tokens must be ints in [0, {cfg.vocab_size})")
-        new = int(r.get("max_new_tokens", 16))
-        if new < 1:
-            raise ValueError("max_new_tokens must be >= 1")
-        if len(toks) + new > cfg.n_positions:
-            raise ValueError(f"prompt ({len(toks)}) + max_new_tokens ({new}) exceeds "
-                             f"n_positions ({cfg.n_positions})")
-        temp = float(r.get("temperature", 0.0) or 0.0)
-        if not 0 <= temp < float("inf"):
-            raise ValueError("temperature must be >= 0")
-        top_k = r.get("top_k")
-        top_k = 0 if top_k is None else int(top_k)
-        top_p = r.get("top_p")
-        top_p = 1.0 if top_p is None else float(top_p)
-        if not 0 < top_p <= 1:
-            raise ValueError("top_p must be in (0, 1]")
-        seed = r.get("seed")
-        seed = self.seed if seed is None else int(seed)
-        if not -2 ** 63 <= seed < 2 ** 64:
-            raise ValueError("seed must fit 64 bits")
-        return len(toks), new, temp, top_k, top_p, seed
+        return _request_params(self.model.cfg, self.seed, r)
 
     def _run_sampled(self, reqs, params):
         """One ragged generate call through the device sampler, every parameter per row."""
@@ -168,10 +149,206 @@ class GPT2Server:
         return await self._generate_batch(request)
 
 
+def _request_params(cfg, default_seed, r):
+    """A request's checked (len, new, temperature, top_k, top_p, seed)."""
+    toks = r.get("tokens")
+    if not toks:
+        raise ValueError("request needs a non-empty 'tokens' list")
+    if any(not isinstance(t, int) or not 0 <= t < cfg.vocab_size for t in toks):
+        raise ValueError(f"tokens must be ints in [0, {cfg.vocab_size})")
+    new = int(r.get("max_new_tokens", 16))
+    if new < 1:
+        raise ValueError("max_new_tokens must be >= 1")
+    if len(toks) + new > cfg.n_positions:
+        raise ValueError(f"prompt ({len(toks)}) + max_new_tokens ({new}) exceeds "
+                         f"n_positions ({cfg.n_positions})")
+    temp = float(r.get("temperature", 0.0) or 0.0)
+    if not 0 <= temp < float("inf"):
+        raise ValueError("temperature must be >= 0")
+    top_k = r.get("top_k")
+    top_k = 0 if top_k is None else int(top_k)
+    top_p = r.get("top_p")
+    top_p = 1.0 if top_p is None else float(top_p)
+    if not 0 < top_p <= 1:
+        raise ValueError("top_p must be in (0, 1]")
+    seed = r.get("seed")
+    seed = default_seed if seed is None else int(seed)
+    if not -2 ** 63 <= seed < 2 ** 64:
+        raise ValueError("seed must fit 64 bits")
+    return len(toks), new, temp, top_k, top_p, seed
+
+
+class GPT2EngineServer:
+    """Continuous batching: requests enter and leave a ``GPT2Engine`` of ``slots`` KV-cache
+    slots independently, so a short request never waits for a long one and tokens can be
+    streamed as they are produced. ``__call__`` awaits the whole result,
+    ``{"tokens": [...]}``; ``stream`` (``handle.options(method_name="stream", stream=True)``)
+    yields ``{"tokens": [...new...]}`` chunks, the last one with ``"finished": True``. A
+    request's tokens are those of ``generate(..., seeds=[seed])`` on that request alone,
+    cut after the first ``eos_token_id``.
+
+    One engine thread owns the model and every GPU call (construction, graph capture,
+    replays). Requests reach it through a thread-safe queue, on which it blocks when idle;
+    results go back to the caller's event loop with ``call_soon_threadsafe``."""
+
+    def __init__(self, config="small", state_dict_path=None, seed=0, slots=None,
+                 eos_token_id=None, device=None, poll_every=None):
+        import queue
+        import threading
+
+        self.cfg = getattr(GPT2Config, config)() if isinstance(config, str) else config
+        self.device = _pick_device(device)
+        self.seed = seed
+        self.engine = None
+        self._inbox = queue.Queue()
+        self._next_key = 0
+        self._failure = None
+        ready = threading.Event()
+        self._thread = threading.Thread(
+            target=self._engine_loop, name="gpt2-engine", daemon=True,
+            args=(state_dict_path, 8 if slots is None else int(slots), eos_token_id,
+                  poll_every, ready))
+        self._thread.start()
+        ready.wait()
+        if self._failure is not None:
+            raise self._failure
+
+    # ------------------------------------------------------------------ the engine thread
+    def _engine_loop(self, state_dict_path, slots, eos_token_id, poll_every, ready):
+        import queue
+
+        from ray_amd.models.gpt2_engine import GPT2Engine
+
+        try:
+            torch.manual_seed(self.seed)
+            model = GPT2(self.cfg)
+            if state_dict_path is not None:
+                model.load_state_dict(torch.load(state_dict_path, map_location="cpu"))
+            if self.device.type == "cuda":
+                torch.cuda.set_device(self.device)
+                model = model.to(self.device, torch.bfloat16)
+            kw = {} if poll_every is None else {"poll_every": int(poll_every)}
+            eng = GPT2Engine(model.eval(), slots=slots, eos_token_id=eos_token_id, **kw)
+            self.engine = eng
+        except BaseException as e:  # noqa: BLE001  (reported to the constructor's caller)
+            self._failure = e
+            return
+        finally:
+            ready.set()
+        sinks = {}  # engine request id -> (key, loop, asyncio queue)
+        rids = {}   # key -> engine request id
+        while True:
+            msgs = []
+            if not eng.has_work():
+                msgs.append(self._inbox.get())  # idle: block, no spinning
+            try:
+                while True:
+                    msgs.append(self._inbox.get_nowait())
+            except queue.Empty:
+                pass
+            for msg in msgs:
+                if msg[0] == "stop":
+                    return
+                if msg[0] == "cancel":
+                    rid = rids.pop(msg[1], None)
+                    if rid is not None:
+                        eng.cancel(rid)
+                        sinks.pop(rid, None)
+                    continue
+                _, key, req, p, loop, sink = msg
+                try:
+                    rid = eng.submit(req["tokens"], p[1], temperature=p[2], top_k=p[3],
+                                     top_p=p[4], seed=p[5])
+                except ValueError as e:
+                    loop.call_soon_threadsafe(sink.put_nowait, ("error", f"ValueError: {e}"))
+                    continue
+                sinks[rid] = (key, loop, sink)
+                rids[key] = rid
+            if not eng.has_work():
+                continue
+            try:
+                events = eng.step()
+            except BaseException as e:  # noqa: BLE001  (every waiting caller learns of it)
+                for key, loop, sink in sinks.values():
+                    loop.call_soon_threadsafe(sink.put_nowait,
+                                              ("error", f"{type(e).__name__}: {e}"))
+                self._failure = e
+                return
+            for rid, new, finished in events:
+                key, loop, sink = sinks[rid]
+                if finished:
+                    del sinks[rid]
+                    rids.pop(key, None)
+                loop.call_soon_threadsafe(sink.put_nowait, ("tokens", new, finished))
+
+    def close(self):
+        self._inbox.put(("stop",))
+        self._thread.join()
+
+    # ------------------------------------------------------------------ the callers' side
+    async def _chunks(self, request):
+        """The request's ("tokens", new, finished) items as the engine's polls produce
+        them, or one ("error", message); cancels the request when the consumer leaves."""
+        import asyncio
+
+        if not isinstance(request, dict):  # HTTP: a JSON body
+            request = await request.json()
+        try:
+            p = _request_params(self.cfg, self.seed, request)
+        except Exception as e:  # noqa: BLE001  (a bad request touches nothing else)
+            yield ("error", f"{type(e).__name__}: {e}")
+            return
+        if self._failure is not None:
+            yield ("error", f"engine stopped: {self._failure}")
+            return
+        key = self._next_key
+        self._next_key += 1
+        sink = asyncio.Queue()
+        self._inbox.put(("submit", key, request, p, asyncio.get_running_loop(), sink))
+        finished = False
+        try:
+            while not finished:
+                item = await sink.get()
+                finished = item[0] == "error" or item[2]
+                yield item
+        finally:
+            if not finished:  # the generator was closed or the task cancelled
+                self._inbox.put(("cancel", key))
+
+    async def __call__(self, request):
+        toks = []
+        async for item in self._chunks(request):
+            if item[0] == "error":
+                return {"error": item[1]}
+            toks.extend(item[1])
+        return {"tokens": toks}
+
+    async def stream(self, request):
+        chunks = self._chunks(request)
+        try:
+            async for item in chunks:
+                if item[0] == "error":
+                    yield {"error": item[1], "finished": True}
+                elif item[2]:
+                    yield {"tokens": item[1], "finished": True}
+                else:
+                    yield {"tokens": item[1]}
+        finally:
+            await chunks.aclose()
+
+
 def build_gpt2_app(config="small", state_dict_path=None, seed=0, max_batch_size=8,
-                   batch_wait_timeout_s=0.01, device=None):
+                   batch_wait_timeout_s=0.01, device=None, continuous=False, slots=None,
+                   eos_token_id=None):
     """A Serve application around one ``GPT2Server`` replica (``serve.run`` it). ``config``
     names a ``GPT2Config`` preset; without ``state_dict_path`` the weights are the seeded
-    random init. ``device`` None: the GPU assigned to the replica, else the CPU."""
+    random init. ``device`` None: the GPU assigned to the replica, else the CPU.
+
+    ``continuous=True`` binds a ``GPT2EngineServer`` instead: continuous batching over
+    ``slots`` (default 8) KV-cache slots with streaming, requests ending at
+    ``eos_token_id``; ``max_batch_size`` and ``batch_wait_timeout_s`` do not apply."""
+    if continuous:
+        dep = deployment(GPT2EngineServer, name="GPT2EngineServer")
+        return dep.bind(config, state_dict_path, seed, slots, eos_token_id, device)
     dep = deployment(GPT2Server, name="GPT2Server")
     return dep.bind(config, state_dict_path, seed, max_batch_size, batch_wait_timeout_s, device)
