@@ -26,7 +26,7 @@ BUILD_DIR = os.path.join(HERE, "build")
 HIP_LIB = os.path.join(HERE, "libray_amd_hip.so")
 ARCH = os.environ.get("RAY_AMD_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-NO_SLP_SOURCES = {"attn.hip", "layernorm.hip", "gelu.hip"}
+NO_SLP_SOURCES = {"attn.hip", "attn_extend.hip", "layernorm.hip", "gelu.hip"}
 
 
 def _newer(target: str, sources: list[str]) -> bool:

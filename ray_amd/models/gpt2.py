@@ -30,6 +30,8 @@ MI355X-first choices:
   host sync) and the whole step, sampler included, is one graph replay. ``prefill_into``
   writes a prefill's K/V into device-chosen rows of a wider cache (ops/csrc/kv_slots.hip):
   the admission path of the continuous-batching engine, models/gpt2_engine.py.
+  ``extend_into`` continues rows of such a cache with several new tokens each
+  (ops/csrc/attn_extend.hip): the engine's shared prompt prefixes and chunked prefill.
 """
 
 from __future__ import annotations
@@ -336,6 +338,57 @@ class GPT2(nn.Module):
         sl = slots.long()
         sl = torch.where((sl >= 0) & (sl < S), sl, S)
         cache.lens.copy_(torch.cat([cache.lens, cache.lens.new_zeros(1)]).scatter_(0, sl, lens)[:S])
+        return logits
+
+    @torch.no_grad()
+    def extend_into(self, idx, n_new, cache: KVCache, slots, base):
+        """Continues sequences that already sit in ``cache``: row b of ``idx`` [Bn, Tn]
+        (right-padded, true counts ``n_new`` [Bn], >= 1) holds the tokens at positions
+        ``base[b] .. base[b] + n_new[b] - 1`` of the sequence in row ``slots[b]``, whose first
+        ``base[b]`` positions are cached (``slots`` and ``base`` int32 [Bn] on the device,
+        ``slots`` distinct). Every layer goes through ``rf.attn_extend`` (the new K/V are
+        appended to the row, the new queries attend over the cached positions and, causally,
+        over each other), any Tn, no padding to a multiple of 128. ``base`` is the caller's
+        to keep: it is NOT read from ``cache.lens`` (the engine's device step pins the
+        ``lens`` of every slot that is not decoding). Writes ``cache.lens[slots] = base +
+        n_new`` IN PLACE for the rows ``rf.attn_extend`` treats as active and returns the
+        logits of each row's last real token, [Bn, vocab_size]. No host synchronisation."""
+        cfg = self.cfg
+        Bn, Tn = idx.shape
+        for name, t in (("slots", slots), ("base", base)):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or \
+                    t.shape != (Bn,) or t.device != idx.device:
+                raise ValueError(f"{name} must be an int32 tensor of shape [{Bn}] on "
+                                 f"{idx.device}")
+        if Bn < 1 or Tn < 1:
+            raise ValueError("extend_into needs at least one token in every row")
+        n_new = torch.as_tensor(n_new, device=idx.device).to(torch.int32)
+        H, hd = cfg.n_head, cfg.n_embd // cfg.n_head
+        # the padding's positions are clamped into the table; its outputs are dropped
+        pos = (base.long().view(Bn, 1) + torch.arange(Tn, device=idx.device)).clamp(
+            0, cfg.n_positions - 1)
+        x = self.wte[idx] + self.wpe[pos]
+        x, h = self.h[0].ln_1.fork(x)
+        for i, blk in enumerate(self.h):
+            qkv = F.linear(h, blk.c_attn_w, blk.c_attn_b).view(Bn, Tn, 3, H, hd)
+            y = rf.attn_extend(qkv, cache.k[i], cache.v[i], slots, base, n_new)
+            a = F.linear(y.reshape(Bn, Tn, cfg.n_embd), blk.c_proj_w)
+            x, h = rf.residual_layer_norm(a, blk.c_proj_b, x, blk.ln_2.weight, blk.ln_2.bias,
+                                          blk.ln_2.eps)
+            nxt = self.h[i + 1].ln_1 if i + 1 < len(self.h) else self.ln_f
+            m = F.linear(rf.bias_gelu(F.linear(h, blk.c_fc_w), blk.c_fc_b), blk.mlp_proj_w)
+            x, h = rf.residual_layer_norm(m, blk.mlp_proj_b, x, nxt.weight, nxt.bias, nxt.eps)
+        last = (n_new.long() - 1).clamp(0, Tn - 1)
+        hl = h[torch.arange(Bn, device=idx.device), last]
+        logits = F.linear(hl, self.wte)[:, : cfg.vocab_size]
+        # a row that attn_extend skipped lands in a spare entry, as in prefill_into
+        S = cache.lens.shape[0]
+        sl, bl, nl = slots.long(), base.long(), n_new.long()
+        ok = (sl >= 0) & (sl < S) & (bl >= 0) & (nl >= 1) & (nl <= Tn) & \
+            (bl + nl <= cache.k.shape[3])
+        sl = torch.where(ok, sl, S)
+        cache.lens.copy_(torch.cat([cache.lens, cache.lens.new_zeros(1)])
+                         .scatter_(0, sl, (bl + nl).to(torch.int32))[:S])
         return logits
 
     def _prefill(self, idx, lens, store):

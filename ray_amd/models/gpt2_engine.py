@@ -28,6 +28,24 @@ static batching at both measured widths, at 1 only at S = 8 (profiles/r10/engine
 price: tokens arrive in groups of up to ``poll_every``, and a slot that finishes inside a
 group stays idle until the group ends.
 
+Shared prompt prefixes (``prefix_slots=P``): ``add_prefix(tokens)`` prefills a prefix once
+into a row of a second KV cache, and ``submit(tokens, ..., prefix=pid)`` takes ``tokens`` as
+the continuation of it. At admission the slot gets the prefix's positions by one
+``rf.kv_copy`` per round (all layers, K and V) and only the continuation runs through the
+model, ``GPT2.extend_into`` (``rf.attn_extend``: new queries over cached keys).
+
+Chunked prefill (``prefill_chunk=C``): no more than C prompt tokens per request are processed
+per ``step()``, so a long prompt stalls the running requests for one chunk and not for its
+whole prefill. A slot whose prompt is not finished is FILLING: occupied, cancellable, but
+inactive on the device (``slot_advance`` keeps its ``cache.lens`` pinned, ``decode_step``
+leaves its cache row alone) and it produces no event; the host keeps its ``base``, the
+positions cached so far. Each ``step()`` admits, runs one chunk round for all filling slots
+together (rows at ``base == 0`` through ``prefill_into``, the others through ONE ragged
+``extend_into``), installs the rows whose prompt just completed and runs the device steps.
+The captured step is untouched. With both options at their defaults the engine does what it
+did without them. The guarantee above holds with ``prefix + tokens`` as the prompt, for every
+``prefill_chunk``.
+
 Single-threaded by contract: every call comes from one thread."""
 
 from __future__ import annotations
@@ -42,16 +60,18 @@ from ray_amd.ops import functional as rf
 
 
 class _Request:
-    __slots__ = ("rid", "tokens", "max_new", "temperature", "top_k", "top_p", "seed")
+    __slots__ = ("rid", "tokens", "max_new", "temperature", "top_k", "top_p", "seed", "pid")
 
-    def __init__(self, rid, tokens, max_new, temperature, top_k, top_p, seed):
+    def __init__(self, rid, tokens, max_new, temperature, top_k, top_p, seed, pid=None):
+        # tokens: the whole prompt (the prefix's tokens included); pid: the prefix it names
         self.rid, self.tokens, self.max_new = rid, tokens, max_new
         self.temperature, self.top_k, self.top_p, self.seed = temperature, top_k, top_p, seed
+        self.pid = pid
 
 
 class GPT2Engine:
     def __init__(self, model: GPT2, slots=8, max_len=None, eos_token_id=None, graph=None,
-                 poll_every=8):
+                 poll_every=8, prefix_slots=0, prefill_chunk=None):
         cfg = model.cfg
         dev = model.wte.device
         S = int(slots)
@@ -59,6 +79,10 @@ class GPT2Engine:
             raise ValueError("slots must be >= 1")
         if int(poll_every) < 1:
             raise ValueError("poll_every must be >= 1")
+        if int(prefix_slots) < 0:
+            raise ValueError("prefix_slots must be >= 0")
+        if prefill_chunk is not None and int(prefill_chunk) < 1:
+            raise ValueError("prefill_chunk must be None or >= 1")
         if graph is None:
             graph = dev.type == "cuda"
         if graph and dev.type != "cuda":
@@ -89,6 +113,17 @@ class GPT2Engine:
         self._slot_req = [None] * S  # the request running in each slot
         self._seen_host = [0] * S
         self._next_rid = 0
+        # a filling slot's base: prompt positions cached so far (None: not filling)
+        self._fill = [None] * S
+        self.prefill_chunk = None if prefill_chunk is None else int(prefill_chunk)
+        self.prefix_slots = int(prefix_slots)
+        self.prefix_cache = None
+        if self.prefix_slots:
+            self.prefix_cache = KVCache(cfg, self.prefix_slots, self.max_len, dev,
+                                        model.wte.dtype)
+        self._prefixes = {}  # pid -> (row of prefix_cache, tokens)
+        self._prefix_free = list(range(self.prefix_slots))
+        self._next_pid = 0
         self._graph = None
         if graph:
             from ray_amd.ops.graph_lock import CAPTURE_LOCK
@@ -120,18 +155,56 @@ class GPT2Engine:
         self.steps += 1
 
     # ------------------------------------------------------------------ requests
-    def submit(self, tokens, max_new_tokens, temperature=0.0, top_k=None, top_p=None, seed=0):
-        """Queues a request and returns its id; a bad request raises ``ValueError`` and
-        queues nothing."""
+    def _checked_tokens(self, tokens, what):
         cfg = self.model.cfg
         if isinstance(tokens, torch.Tensor):
             tokens = tokens.tolist()
         tokens = list(tokens)
         if not tokens:
-            raise ValueError("a request needs a non-empty prompt")
+            raise ValueError(f"a {what} needs a non-empty prompt")
         if any(isinstance(t, bool) or not isinstance(t, int) or not 0 <= t < cfg.vocab_size
                for t in tokens):
             raise ValueError(f"tokens must be ints in [0, {cfg.vocab_size})")
+        return tokens
+
+    def add_prefix(self, tokens):
+        """Prefills ``tokens`` (1 <= len < max_len) once into a row of the prefix store and
+        returns the prefix's id for ``submit(..., prefix=pid)``. ``ValueError`` for bad
+        tokens or a full store (``prefix_slots`` rows), which then holds what it held."""
+        tokens = self._checked_tokens(tokens, "prefix")
+        if len(tokens) >= self.max_len:
+            raise ValueError(f"prefix ({len(tokens)}) leaves no room in max_len "
+                             f"({self.max_len})")
+        if not self._prefix_free:
+            raise ValueError(f"the prefix store is full ({self.prefix_slots} rows)")
+        row = self._prefix_free.pop(0)
+        dev = self.device
+        self.model.prefill_into(torch.tensor([tokens], dtype=torch.long).to(dev),
+                                torch.tensor([len(tokens)], dtype=torch.int32).to(dev),
+                                self.prefix_cache,
+                                torch.tensor([row], dtype=torch.int32).to(dev))
+        pid = self._next_pid
+        self._next_pid += 1
+        self._prefixes[pid] = (row, tokens)
+        return pid
+
+    def drop_prefix(self, pid):
+        """Frees the prefix's row of the store. Requests already admitted keep their copy;
+        a request still queued is prefilled whole when its turn comes."""
+        if pid not in self._prefixes:
+            raise ValueError(f"unknown prefix {pid!r}")
+        self._prefix_free.append(self._prefixes.pop(pid)[0])
+
+    def submit(self, tokens, max_new_tokens, temperature=0.0, top_k=None, top_p=None, seed=0,
+               prefix=None):
+        """Queues a request and returns its id; a bad request raises ``ValueError`` and
+        queues nothing. ``prefix``: an ``add_prefix`` id; ``tokens`` is then the non-empty
+        continuation and the request's prompt is the prefix's tokens followed by it."""
+        tokens = self._checked_tokens(tokens, "request")
+        if prefix is not None:
+            if not isinstance(prefix, int) or prefix not in self._prefixes:
+                raise ValueError(f"unknown prefix {prefix!r}")
+            tokens =self._prefixes[prefix][1] + tokens
         max_new = int(max_new_tokens)
         if max_new < 1:
             raise ValueError("max_new_tokens must be >= 1")
@@ -153,7 +226,8 @@ class GPT2Engine:
         top_k = max(0, min(top_k, 2 ** 31 - 1))
         rid = self._next_rid
         self._next_rid += 1
-        self._queue.append(_Request(rid, tokens, max_new, temperature, top_k, top_p, seed))
+        self._queue.append(_Request(rid, tokens, max_new, temperature, top_k, top_p, seed,
+                                    prefix))
         return rid
 
     def cancel(self, rid):
@@ -168,6 +242,7 @@ class GPT2Engine:
                 self.active[s] = 0
                 self.cache.lens[s] = rf.SLOT_INACTIVE
                 self._slot_req[s] = None
+                self._fill[s] = None
                 return True
         return False
 
@@ -176,7 +251,12 @@ class GPT2Engine:
 
     @property
     def num_active(self):
+        """Occupied slots: decoding or filling."""
         return sum(r is not None for r in self._slot_req)
+
+    @property
+    def num_filling(self):
+        return sum(b is not None for b in self._fill)
 
     @property
     def num_queued(self):
@@ -188,22 +268,67 @@ class GPT2Engine:
         reqs = []
         while self._queue and len(reqs) < len(free):
             reqs.append(self._queue.popleft())
-        if not reqs:
-            return
+        # an admitted request starts FILLING at base 0, or at its prefix's length with the
+        # prefix's K/V copied into the slot: one kv_copy per round, all layers
+        copies = []
+        for s, r in zip(free, reqs):
+            self._slot_req[s] = r
+            self._fill[s] = 0
+            if r.pid in self._prefixes:  # (dropped meanwhile: the whole prompt is prefilled)
+                row, head = self._prefixes[r.pid]
+                copies.append([row, s, len(head)])
+                self._fill[s] = len(head)
+        if copies:
+            c = torch.tensor(copies, dtype=torch.int32).to(self.device)
+            rf.kv_copy(self.prefix_cache.k, self.prefix_cache.v, self.cache.k, self.cache.v,
+                       c[:, 0].contiguous(), c[:, 1].contiguous(), c[:, 2].contiguous())
+
+    def _fill_round(self):
+        """One chunk of prompt for every filling slot: the rows at base 0 through one ragged
+        ``prefill_into``, the others (prefix continuations, later chunks) through one ragged
+        ``extend_into``; the rows whose prompt is complete become active."""
+        groups = [[s for s, b in enumerate(self._fill) if b is not None and (b > 0) == ext]
+                  for ext in (False, True)]
+        for ext, rows in zip((False, True), groups):
+            if rows:
+                self._fill_rows(rows, ext)
+
+    def _fill_rows(self, rows, ext):
         dev = self.device
-        slots = free[: len(reqs)]
-        lens = [len(r.tokens) for r in reqs]
+        reqs = [self._slot_req[s] for s in rows]
+        bases = [self._fill[s] for s in rows]
+        lens = [len(r.tokens) - b for r, b in zip(reqs, bases)]
+        if self.prefill_chunk is not None:
+            lens = [min(n, self.prefill_chunk) for n in lens]
         idx = torch.zeros(len(reqs), max(lens), dtype=torch.long)
         for b, r in enumerate(reqs):
-            idx[b, : lens[b]] = torch.tensor(r.tokens, dtype=torch.long)
-        # three uploads per round, however many requests it admits
-        ints = torch.tensor([[s, n, r.top_k, r.max_new, r.seed]
-                             for s, n, r in zip(slots, lens, reqs)], dtype=torch.int64).to(dev)
+            idx[b, : lens[b]] = torch.tensor(r.tokens[bases[b]: bases[b] + lens[b]],
+                                             dtype=torch.long)
+        # three uploads per round and path, however many requests it feeds
+        ints = torch.tensor([[s, n, r.top_k, r.max_new, r.seed, b]
+                             for s, n, r, b in zip(rows, lens, reqs, bases)],
+                            dtype=torch.int64).to(dev)
         flts = torch.tensor([[r.temperature, r.top_p] for r in reqs],
                             dtype=torch.float32).to(dev)
         sl = ints[:, 0]
-        logits = self.model.prefill_into(idx.to(dev), ints[:, 1].to(torch.int32), self.cache,
-                                         sl.to(torch.int32))
+        if ext:
+            logits = self.model.extend_into(idx.to(dev), ints[:, 1].to(torch.int32), self.cache,
+                                            sl.to(torch.int32), ints[:, 5].to(torch.int32))
+        else:
+            logits = self.model.prefill_into(idx.to(dev), ints[:, 1].to(torch.int32),
+                                             self.cache, sl.to(torch.int32))
+        done = [j for j, r in enumerate(reqs) if bases[j] + lens[j] == len(r.tokens)]
+        for j, s in enumerate(rows):
+            self._fill[s] = bases[j] + lens[j]
+        if len(done) < len(rows):
+            # the unfinished rows stay inactive on the device: the model wrote their lens
+            pend = torch.tensor([rows[j] for j in range(len(rows)) if j not in done]).to(dev)
+            self.cache.lens.index_fill_(0, pend, rf.SLOT_INACTIVE)
+            if not done:
+                return
+            sel = torch.tensor(done).to(dev)
+            ints, flts, logits = ints[sel], flts[sel], logits[sel]
+            sl = ints[:, 0]
         self.logits.index_copy_(0, sl, logits)
         self.top_k.index_copy_(0, sl, ints[:, 2].to(torch.int32))
         self.max_new.index_copy_(0, sl, ints[:, 3].to(torch.int32))
@@ -213,9 +338,9 @@ class GPT2Engine:
         self.n_out.index_fill_(0, sl, 0)
         self._seen.index_fill_(0, sl, 0)
         self.active.index_fill_(0, sl, 1)
-        for s, r in zip(slots, reqs):
-            self._slot_req[s] = r
-            self._seen_host[s] = 0
+        for j in done:
+            self._fill[rows[j]] = None
+            self._seen_host[rows[j]] = 0
 
     # ------------------------------------------------------------------ poll
     def _poll(self):
@@ -227,7 +352,7 @@ class GPT2Engine:
         self._seen.copy_(self.n_out)
         events = []
         for s, r in enumerate(self._slot_req):
-            if r is None:
+            if r is None or self._fill[s] is not None:  # filling: inactive, not finished
                 continue
             n, act = host[s][0], host[s][1]
             new = host[s][2: 2 + n - self._seen_host[s]]
@@ -239,10 +364,13 @@ class GPT2Engine:
         return events
 
     def step(self):
-        """Admits queued requests into free slots, runs ``poll_every`` device steps and
-        polls: ``[(rid, new_tokens, finished), ...]`` for the slots that produced tokens."""
+        """Admits queued requests into free slots, feeds every filling slot one chunk of its
+        prompt (the whole prompt without ``prefill_chunk``), runs ``poll_every`` device steps
+        if any slot is decoding and polls: ``[(rid, new_tokens, finished), ...]`` for the
+        slots that produced tokens."""
         self._admit()
-        if self.num_active == 0:
+        self._fill_round()
+        if self.num_active == self.num_filling:
             return []
         for _ in range(self.poll_every):
             self._run_step()

@@ -1,6 +1,6 @@
 // Slot bookkeeping of the continuous-batching GPT-2 engine (models/gpt2_engine.py): a
 // persistent K/V cache of S slots that requests enter and leave independently, between
-// replays of one captured decode step. Two entry points, both capturable: every index they
+// replays of one captured decode step. Three entry points, all capturable: every index they
 // use (slot id, length, output column) is read ON THE DEVICE and checked there before it
 // addresses memory; a bad value skips the work and never writes outside a tensor.
 //
@@ -19,6 +19,20 @@
 // H, Bn) with n = min(Tp, Tmax); a workgroup owns 64 positions of one (b, h), K and V, four
 // 16-byte loads per lane in flight before the first store; workgroups past lens[b] exit
 // after reading it. No LDS.
+//
+// ra_kv_copy: the shared-prefix path. Copies cached rows from one cache to another, all
+// layers, K and V, in one launch.
+//
+//   src_k, src_v [L, P, H, Tsrc, 64], dst_k, dst_v [L, S, H, Tdst, 64]
+//   src_rows, dst_rows, lens [Bn] int32
+//
+// For every b with 0 <= src_rows[b] < P, 0 <= dst_rows[b] < S and 0 <= lens[b] <=
+// min(Tsrc, Tdst), every layer l, head h and t < lens[b]:
+// dst[l, dst_rows[b], h, t, :] = src[l, src_rows[b], h, t, :]; any other b is skipped and
+// nothing else is written. Built as ra_kv_insert: grid (ceil(n / 64), L * H, Bn) with
+// n = min(Tsrc, Tdst), a workgroup owns 64 positions of one (l, h, b), K and V, four 16-byte
+// loads per lane in flight before the first store (here both sides are 1 KiB contiguous per
+// wave instruction), no branch after the row-length test, no LDS.
 //
 // ra_slot_advance: the per-token path, after the sampler, one thread per slot.
 //
@@ -75,6 +89,35 @@ __global__ __launch_bounds__(kThreads) void kv_insert_kernel(
   }
 }
 
+__global__ __launch_bounds__(kThreads) void kv_copy_kernel(
+    const bf16_t* __restrict__ sk, const bf16_t* __restrict__ sv, bf16_t* __restrict__ dk,
+    bf16_t* __restrict__ dv, const int* __restrict__ src_rows, const int* __restrict__ dst_rows,
+    const int* __restrict__ lens, int H, int P, int Tsrc, int S, int Tdst) {
+  const int b = blockIdx.z, l = blockIdx.y / H, h = blockIdx.y % H;
+  const int sr = src_rows[b], dr = dst_rows[b], len = lens[b];
+  if (sr < 0 || sr >= P || dr < 0 || dr >= S || len < 0 || len > min(Tsrc, Tdst)) return;
+  const int t0 = blockIdx.x * kBlockRows;
+  if (t0 >= len) return;
+  const int r = threadIdx.x >> 3, c = threadIdx.x & 7;
+  const long src0 = ((((long)l * P + sr) * H + h) * Tsrc) * kD + c * 8;
+  const long dst0 = ((((long)l * S + dr) * H + h) * Tdst) * kD + c * 8;
+  // As kv_insert_kernel: no branch from here on, a lane past the row's end moves position
+  // len - 1 again (t0 < len <= min(Tsrc, Tdst): a real position of both caches).
+  uint4 kk[kPasses], vv[kPasses];
+#pragma unroll
+  for (int u = 0; u < kPasses; ++u) {
+    const int t = min(t0 + u * kRowsPerPass + r, len - 1);
+    kk[u] = *reinterpret_cast<const uint4*>(sk + src0 + (long)t * kD);
+    vv[u] = *reinterpret_cast<const uint4*>(sv + src0 + (long)t * kD);
+  }
+#pragma unroll
+  for (int u = 0; u < kPasses; ++u) {
+    const int t = min(t0 + u * kRowsPerPass + r, len - 1);
+    *reinterpret_cast<uint4*>(dk + dst0 + (long)t * kD) = kk[u];
+    *reinterpret_cast<uint4*>(dv + dst0 + (long)t * kD) = vv[u];
+  }
+}
+
 __global__ __launch_bounds__(64) void slot_advance_kernel(
     const long* __restrict__ tok, int* __restrict__ lens, int* __restrict__ n_out,
     const int* __restrict__ max_new, unsigned char* __restrict__ active, long* __restrict__ out,
@@ -114,6 +157,25 @@ RA_EXPORT int ra_kv_insert(const void* qkv, void* k_cache, void* v_cache, const 
   hipLaunchKernelGGL(kv_insert_kernel, dim3((n + kBlockRows - 1) / kBlockRows, H, Bn),
                      dim3(kThreads), 0, st, (const bf16_t*)qkv, (bf16_t*)k_cache,
                      (bf16_t*)v_cache, slots, lens, Tp, H, S, Tmax);
+  return hipGetLastError();
+}
+
+// All four caches 16-byte aligned, src and dst distinct tensors. Runs on the caller's stream;
+// no host synchronisation, no allocation; the three index vectors stay on the device and are
+// only read.
+RA_EXPORT int ra_kv_copy(const void* src_k, const void* src_v, void* dst_k, void* dst_v,
+                         const int* src_rows, const int* dst_rows, const int* lens, int Bn, int L,
+                         int H, int P, int Tsrc, int S, int Tdst, hipStream_t st) {
+  if (Bn <= 0 || L <= 0 || H <= 0 || P <= 0 || S <= 0 || Tsrc <= 0 || Tdst <= 0 || Bn > 65535 ||
+      (long)L * H > 65535 || Tsrc > (1 << 22) || Tdst > (1 << 22))
+    return hipErrorInvalidValue;
+  if ((((uintptr_t)src_k | (uintptr_t)src_v | (uintptr_t)dst_k | (uintptr_t)dst_v) & 15) ||
+      src_rows == nullptr || dst_rows == nullptr || lens == nullptr)
+    return hipErrorInvalidValue;
+  const int n = Tsrc < Tdst ? Tsrc : Tdst;
+  hipLaunchKernelGGL(kv_copy_kernel, dim3((n + kBlockRows - 1) / kBlockRows, L * H, Bn),
+                     dim3(kThreads), 0, st, (const bf16_t*)src_k, (const bf16_t*)src_v,
+                     (bf16_t*)dst_k, (bf16_t*)dst_v, src_rows, dst_rows, lens, H, P, Tsrc, S, Tdst);
   return hipGetLastError();
 }
 

@@ -690,6 +690,106 @@ def kv_insert(qkv, k_cache, v_cache, slots, lens):
           "kv_insert")
 
 
+def attn_extend(qkv_new, k_cache, v_cache, slots, base, n_new, scale=None):
+    """Several new tokens for rows that already hold cached positions: ``qkv_new``
+    [Bn, Tn, 3, H, D] is the packed c_attn output of the right-padded new tokens (any
+    Tn >= 1), the caches are [S, H, Tmax, D] and written IN PLACE, ``slots``, ``base`` and
+    ``n_new`` are int32 [Bn] on the tensors' device. Row b is active when 0 <= slots[b] < S,
+    base[b] >= 0, 1 <= n_new[b] <= Tn and base[b] + n_new[b] <= Tmax; it appends its
+    ``n_new[b]`` K/V rows at positions base[b].. of cache row ``slots[b]`` (bitwise) and
+    query i attends over keys 0 .. base[b] + i. Returns [Bn, Tn, H, D]: zero for the padding
+    queries i >= n_new[b] and for inactive rows, which write nothing. The three vectors are
+    only read, on the device, and bounds-checked there: the call is graph-capturable.
+    ``slots`` must be DISTINCT among the active rows (two rows appending to one cache row
+    are the caller's error). An active row's output bits depend on its own ``base``,
+    ``n_new`` and data only, never on Bn, Tn, its slot id or the other rows.
+    Semantics: ``reference.attn_extend``.
+
+    HIP MFMA kernel (ops/csrc/attn_extend.hip: an append launch, then the attention launch)
+    for bf16, D == 64 GPU tensors; CPU tensors, other dtypes and other head sizes use the
+    plain-torch reference. Inference only: raises on tensors that require grad."""
+    if qkv_new.requires_grad or k_cache.requires_grad or v_cache.requires_grad:
+        raise RuntimeError("attn_extend is an inference op: run it under torch.no_grad() on "
+                           "tensors that do not require grad")
+    if qkv_new.dim() != 5 or qkv_new.shape[2] != 3:
+        raise ValueError(f"attn_extend: qkv_new must be [Bn, Tn, 3, H, D], got "
+                         f"{tuple(qkv_new.shape)}")
+    Bn, Tn, _, H, D = qkv_new.shape
+    if k_cache.shape != v_cache.shape or k_cache.dim() != 4 or k_cache.shape[1] != H or \
+            k_cache.shape[3] != D:
+        raise ValueError("attn_extend: the caches must be [S, H, Tmax, D]")
+    S, _, Tmax, _ = k_cache.shape
+    if min(Bn, Tn, H, S, Tmax) < 1:
+        raise ValueError("attn_extend: empty qkv_new or cache")
+    if k_cache.dtype != v_cache.dtype or k_cache.device != qkv_new.device or \
+            v_cache.device != qkv_new.device:
+        raise ValueError("attn_extend: qkv_new and the caches must share a device, the caches "
+                         "a dtype")
+    for name, t in (("slots", slots), ("base", base), ("n_new", n_new)):
+        _int_vec(name, "attn_extend", t, Bn, qkv_new)
+    if scale is None:
+        scale = D ** -0.5
+    if not float(scale) > 0:
+        raise ValueError("attn_extend: scale must be > 0")
+    if not (_hip(qkv_new) and qkv_new.dtype == torch.bfloat16 and D == 64
+            and k_cache.dtype == torch.bfloat16):
+        return ref.attn_extend(qkv_new, k_cache, v_cache, slots, base, n_new, scale)
+    if not (k_cache.is_contiguous() and v_cache.is_contiguous()):
+        raise ValueError("attn_extend: the caches are written in place and must be contiguous")
+    qkv_new = qkv_new.contiguous()
+    out = torch.empty((Bn, Tn, H, D), device=qkv_new.device, dtype=torch.bfloat16)
+    check(_lib.lib().ra_attn_extend(ptr(qkv_new), ptr(k_cache), ptr(v_cache),
+                                    ptr(slots.contiguous()), ptr(base.contiguous()),
+                                    ptr(n_new.contiguous()), ptr(out), Bn, Tn, H, S, Tmax,
+                                    float(scale), stream_ptr()), "attn_extend")
+    return out
+
+
+def kv_copy(src_k, src_v, dst_k, dst_v, src_rows, dst_rows, lens):
+    """Copies cached rows from one cache to another, all layers, K and V, in one launch:
+    ``src_k``, ``src_v`` [L, P, H, Tsrc, D], ``dst_k``, ``dst_v`` [L, S, H, Tdst, D] (written
+    IN PLACE), ``src_rows``, ``dst_rows`` and ``lens`` int32 [Bn] on the tensors' device.
+    For every b with 0 <= src_rows[b] < P, 0 <= dst_rows[b] < S and 0 <= lens[b] <=
+    min(Tsrc, Tdst): ``dst[l, dst_rows[b], h, t] = src[l, src_rows[b], h, t]`` for
+    t < lens[b], bitwise; any other b is skipped, nothing else is written. The vectors are
+    only read, on the device: graph-capturable. Two rows naming one destination are the
+    caller's error; source and destination must not share memory.
+
+    HIP kernel (ops/csrc/kv_slots.hip) for bf16, D == 64 GPU tensors; CPU tensors, other
+    dtypes and other head sizes use the plain-torch reference."""
+    for name, t in (("src_k", src_k), ("src_v", src_v), ("dst_k", dst_k), ("dst_v", dst_v)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 5:
+            raise ValueError(f"kv_copy: {name} must be [L, rows, H, T, D]")
+    if src_k.shape != src_v.shape or dst_k.shape != dst_v.shape:
+        raise ValueError("kv_copy: a cache's K and V must have one shape")
+    L, P, H, Tsrc, D = src_k.shape
+    S, Tdst = dst_k.shape[1], dst_k.shape[3]
+    if dst_k.shape != (L, S, H, Tdst, D):
+        raise ValueError(f"kv_copy: the caches must agree in L, H and D, got "
+                         f"{tuple(src_k.shape)} and {tuple(dst_k.shape)}")
+    if min(L, P, H, Tsrc, D, S, Tdst) < 1:
+        raise ValueError("kv_copy: empty cache")
+    if len({t.dtype for t in (src_k, src_v, dst_k, dst_v)}) != 1 or \
+            len({t.device for t in (src_k, src_v, dst_k, dst_v)}) != 1:
+        raise ValueError("kv_copy: the four caches must share a dtype and a device")
+    if not isinstance(src_rows, torch.Tensor) or src_rows.dim() != 1 or src_rows.shape[0] < 1:
+        raise ValueError("kv_copy: src_rows must be an int32 tensor of shape [Bn]")
+    Bn = src_rows.shape[0]
+    for name, t in (("src_rows", src_rows), ("dst_rows", dst_rows), ("lens", lens)):
+        _int_vec(name, "kv_copy", t, Bn, src_k)
+    if not (_hip(src_k) and src_k.dtype == torch.bfloat16 and D == 64):
+        return ref.kv_copy(src_k, src_v, dst_k, dst_v, src_rows, dst_rows, lens)
+    for name, t in (("src_k", src_k), ("src_v", src_v), ("dst_k", dst_k), ("dst_v", dst_v)):
+        if not t.is_contiguous():
+            raise ValueError(f"kv_copy: {name} must be contiguous")
+    if L * H > 65535:
+        raise ValueError("kv_copy: L * H must not exceed 65535")
+    check(_lib.lib().ra_kv_copy(ptr(src_k), ptr(src_v), ptr(dst_k), ptr(dst_v),
+                                ptr(src_rows.contiguous()), ptr(dst_rows.contiguous()),
+                                ptr(lens.contiguous()), Bn, L, H, P, Tsrc, S, Tdst,
+                                stream_ptr()), "kv_copy")
+
+
 def slot_advance(tok, lens, n_out, max_new, active, out, eos_token_id=None):
     """The continuous-batching engine's bookkeeping after the sampler, one launch, IN
     PLACE: an active slot with ``n_out[s] < cap`` stores ``out[s, n_out[s]] = tok[s]``,

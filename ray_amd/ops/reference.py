@@ -98,6 +98,86 @@ def kv_insert(qkv, k_cache, v_cache, slots, lens):
         cache[:, :, :n] = torch.where(take, new, cache[:, :, :n])
 
 
+def _slot_rows(slots, valid, S, Bn):
+    """Which of the Bn rows feeds each of S slots: ``(row [S], fed [S])``; the rows that are
+    not ``valid`` land in a spare entry. No host sync."""
+    dev = slots.device
+    row = torch.full((S + 1,), Bn, dtype=torch.long, device=dev)
+    row.scatter_(0, torch.where(valid, slots, S), torch.arange(Bn, device=dev))
+    row = row[:S]
+    return row.clamp(max=Bn - 1), row < Bn
+
+
+def attn_extend(qkv_new, k_cache, v_cache, slots, base, n_new, scale=None):
+    """Several new tokens for rows that already hold cached positions
+    (ops/csrc/attn_extend.hip semantics): the single definition of them.
+
+    ``qkv_new`` [Bn, Tn, 3, H, D] is the packed q/k/v of the right-padded new tokens, the
+    caches are [S, H, Tmax, D], ``slots``, ``base`` and ``n_new`` integer [Bn]. Row b is
+    ACTIVE when 0 <= slots[b] < S, base[b] >= 0, 1 <= n_new[b] <= Tn and base[b] + n_new[b]
+    <= Tmax. For an active row, ``k_cache[slots[b], h, base[b] + i] = qkv_new[b, i, 1, h]``
+    for i < n_new[b] (V: index 2), IN PLACE and bitwise, and ``out[b, i]`` is the softmax
+    attention of ``qkv_new[b, i, 0]`` over keys 0 .. base[b] + i of that cache row;
+    ``out[b, i]`` for i >= n_new[b] is zero. An inactive row writes nothing and gets zero
+    output; every other cache element keeps its bits. Positions past a row's end are masked
+    out whatever they hold (NaN included). Slots are distinct among the active rows (two
+    active rows naming one slot are the caller's error). Returns [Bn, Tn, H, D] in
+    ``qkv_new``'s dtype. fp32 math, no host sync."""
+    Bn, Tn, _, H, D = qkv_new.shape
+    S, Tmax = k_cache.shape[0], k_cache.shape[2]
+    dev = qkv_new.device
+    if scale is None:
+        scale = D ** -0.5
+    slots, base, n = slots.long(), base.long(), n_new.long()
+    active = (slots >= 0) & (slots < S) & (base >= 0) & (n >= 1) & (n <= Tn) & (base + n <= Tmax)
+    n = torch.where(active, n, torch.zeros_like(n))
+    base = torch.where(active, base, torch.zeros_like(base))
+    # append, seen from the cache: position t of the slot fed by row b takes new token t - base
+    row, fed = _slot_rows(slots, active, S, Bn)
+    t = torch.arange(Tmax, device=dev).view(1, Tmax)
+    rb, rn = base[row].view(S, 1), n[row].view(S, 1)
+    take = (fed.view(S, 1) & (t >= rb) & (t < rb + rn)).view(S, 1, Tmax, 1)
+    src = (t - rb).clamp(0, Tn - 1)  # [S, Tmax]
+    for cache, which in ((k_cache, 1), (v_cache, 2)):
+        new = qkv_new[row.view(S, 1), src, which].transpose(1, 2).to(cache.dtype)  # [S,H,Tmax,D]
+        cache.copy_(torch.where(take, new, cache))
+    # attention over each row's slot
+    sl = slots.clamp(0, S - 1)
+    i = torch.arange(Tn, device=dev).view(1, Tn, 1)
+    tt = t.view(1, 1, Tmax)
+    keep = ((i < n.view(Bn, 1, 1)) & (tt <= base.view(Bn, 1, 1) + i)).unsqueeze(1)  # [Bn,1,Tn,Tmax]
+    q = qkv_new[:, :, 0].float().transpose(1, 2)  # [Bn, H, Tn, D]
+    s = (q @ k_cache[sl].float().transpose(-1, -2)) * scale
+    p = torch.softmax(s.masked_fill(~keep, float("-inf")), -1)
+    p = torch.where(keep, p, torch.zeros_like(p))  # padding and inactive rows: all -inf
+    valid = (tt < (base + n).view(Bn, 1, 1)).view(Bn, 1, Tmax, 1)
+    vf = torch.where(valid, v_cache[sl].float(), torch.zeros((), device=dev))
+    return (p @ vf).transpose(1, 2).to(qkv_new.dtype)
+
+
+def kv_copy(src_k, src_v, dst_k, dst_v, src_rows, dst_rows, lens):
+    """Copies cached rows from one cache to another, all layers (ops/csrc/kv_slots.hip
+    semantics): ``src_k``, ``src_v`` [L, P, H, Tsrc, D], ``dst_k``, ``dst_v`` [L, S, H, Tdst,
+    D], ``src_rows``, ``dst_rows``, ``lens`` integer [Bn]. For every b with 0 <= src_rows[b]
+    < P, 0 <= dst_rows[b] < S and 0 <= lens[b] <= min(Tsrc, Tdst):
+    ``dst[l, dst_rows[b], h, t] = src[l, src_rows[b], h, t]`` for t < lens[b], IN PLACE and
+    bitwise; any other b is skipped and every other element keeps its bits. Two rows naming
+    one destination are the caller's error. No host sync."""
+    P, Tsrc = src_k.shape[1], src_k.shape[3]
+    S, Tdst = dst_k.shape[1], dst_k.shape[3]
+    Bn = src_rows.shape[0]
+    n = min(Tsrc, Tdst)
+    sr, dr, ln = src_rows.long(), dst_rows.long(), lens.long()
+    valid = (sr >= 0) & (sr < P) & (dr >= 0) & (dr < S) & (ln >= 0) & (ln <= n)
+    row, fed = _slot_rows(dr, valid, S, Bn)
+    t = torch.arange(n, device=dst_k.device)
+    take = (fed.view(S, 1) & (t.view(1, n) < ln[row].view(S, 1))).view(1, S, 1, n, 1)
+    from_row = sr[row].clamp(0, P - 1)
+    for src, dst in ((src_k, dst_k), (src_v, dst_v)):
+        new = src[:, from_row, :, :n].to(dst.dtype)  # [L, S, H, n, D]
+        dst[:, :, :, :n] = torch.where(take, new, dst[:, :, :, :n])
+
+
 def slot_advance(tok, lens, n_out, max_new, active, out, eos_token_id=None):
     """The continuous-batching engine's bookkeeping after the sampler
     (ops/csrc/kv_slots.hip semantics), everything IN PLACE: ``tok`` int64 [S], ``lens``,

@@ -25,7 +25,11 @@ plus longest ``max_new_tokens`` would not fit ``n_positions`` is split.
 continuous batching over S KV-cache slots (``models/gpt2_engine.py``). Requests enter and
 leave between replays of one captured decode step, so a 5-token request does not wait for
 a 900-token one, and ``handle.options(method_name="stream", stream=True)`` streams the
-tokens as they are produced. The same request fields and the same per-request guarantee."""
+tokens as they are produced. The same request fields and the same per-request guarantee.
+``prefixes={"name": [tokens], ...}`` registers shared prompt prefixes with the engine at
+start-up (each is prefilled once); a request may then carry ``"prefix": "name"`` and its
+``tokens`` are the continuation: it answers what the request with the whole prompt answers.
+``prefill_chunk=C`` bounds the prompt tokens a request is fed per engine step."""
 
 from __future__ import annotations
 
@@ -82,6 +86,9 @@ class GPT2Server:
 
     def _params(self, r):
         """The request's checked (len, new, temperature, top_k, top_p, seed)."""
+        if r.get("prefix") is not None:
+            raise ValueError("'prefix' needs the continuous engine: build_gpt2_app("
+                             "continuous=True, prefixes=...)")
         return _request_params(self.model.cfg, self.seed, r)
 
     def _run_sampled(self, reqs, params):
@@ -192,7 +199,8 @@ class GPT2EngineServer:
     results go back to the caller's event loop with ``call_soon_threadsafe``."""
 
     def __init__(self, config="small", state_dict_path=None, seed=0, slots=None,
-                 eos_token_id=None, device=None, poll_every=None):
+                 eos_token_id=None, device=None, poll_every=None, prefixes=None,
+                 prefill_chunk=None):
         import queue
         import threading
 
@@ -203,6 +211,9 @@ class GPT2EngineServer:
         self._inbox = queue.Queue()
         self._next_key = 0
         self._failure = None
+        self._prefixes = {k: list(v) for k, v in (prefixes or {}).items()}
+        self._prefill_chunk = prefill_chunk
+        self._pids = {}  # prefix name -> the engine's prefix id
         ready = threading.Event()
         self._thread = threading.Thread(
             target=self._engine_loop, name="gpt2-engine", daemon=True,
@@ -228,7 +239,11 @@ class GPT2EngineServer:
                 torch.cuda.set_device(self.device)
                 model = model.to(self.device, torch.bfloat16)
             kw = {} if poll_every is None else {"poll_every": int(poll_every)}
-            eng = GPT2Engine(model.eval(), slots=slots, eos_token_id=eos_token_id, **kw)
+            eng = GPT2Engine(model.eval(), slots=slots, eos_token_id=eos_token_id,
+                             prefix_slots=len(self._prefixes),
+                             prefill_chunk=self._prefill_chunk, **kw)
+            for name, toks in self._prefixes.items():
+                self._pids[name] = eng.add_prefix(toks)
             self.engine = eng
         except BaseException as e:  # noqa: BLE001  (reported to the constructor's caller)
             self._failure = e
@@ -258,7 +273,8 @@ class GPT2EngineServer:
                 _, key, req, p, loop, sink = msg
                 try:
                     rid = eng.submit(req["tokens"], p[1], temperature=p[2], top_k=p[3],
-                                     top_p=p[4], seed=p[5])
+                                     top_p=p[4], seed=p[5],
+                                     prefix=self._pids.get(req.get("prefix")))
                 except ValueError as e:
                     loop.call_soon_threadsafe(sink.put_nowait, ("error", f"ValueError: {e}"))
                     continue
@@ -295,6 +311,9 @@ class GPT2EngineServer:
             request = await request.json()
         try:
             p = _request_params(self.cfg, self.seed, request)
+            name = request.get("prefix")
+            if name is not None and (not isinstance(name, str) or name not in self._pids):
+                raise ValueError(f"unknown prefix {name!r}")
         except Exception as e:  # noqa: BLE001  (a bad request touches nothing else)
             yield ("error", f"{type(e).__name__}: {e}")
             return
@@ -339,16 +358,21 @@ class GPT2EngineServer:
 
 def build_gpt2_app(config="small", state_dict_path=None, seed=0, max_batch_size=8,
                    batch_wait_timeout_s=0.01, device=None, continuous=False, slots=None,
-                   eos_token_id=None):
+                   eos_token_id=None, prefixes=None, prefill_chunk=None):
     """A Serve application around one ``GPT2Server`` replica (``serve.run`` it). ``config``
     names a ``GPT2Config`` preset; without ``state_dict_path`` the weights are the seeded
     random init. ``device`` None: the GPU assigned to the replica, else the CPU.
 
     ``continuous=True`` binds a ``GPT2EngineServer`` instead: continuous batching over
     ``slots`` (default 8) KV-cache slots with streaming, requests ending at
-    ``eos_token_id``; ``max_batch_size`` and ``batch_wait_timeout_s`` do not apply."""
+    ``eos_token_id``; ``max_batch_size`` and ``batch_wait_timeout_s`` do not apply.
+    ``prefixes`` (``{"name": [tokens], ...}``: shared prompt prefixes a request names with
+    ``"prefix": "name"``) and ``prefill_chunk`` need ``continuous=True``."""
     if continuous:
         dep = deployment(GPT2EngineServer, name="GPT2EngineServer")
-        return dep.bind(config, state_dict_path, seed, slots, eos_token_id, device)
+        return dep.bind(config, state_dict_path, seed, slots, eos_token_id, device, None,
+                        prefixes, prefill_chunk)
+    if prefixes or prefill_chunk is not None:
+        raise ValueError("prefixes and prefill_chunk need continuous=True")
     dep = deployment(GPT2Server, name="GPT2Server")
     return dep.bind(config, state_dict_path, seed, max_batch_size, batch_wait_timeout_s, device)
