@@ -32,6 +32,8 @@ MI355X-first choices:
   the admission path of the continuous-batching engine, models/gpt2_engine.py.
   ``extend_into`` continues rows of such a cache with several new tokens each
   (ops/csrc/attn_extend.hip): the engine's shared prompt prefixes and chunked prefill.
+  The three inference passes (prompt, extend, decode) run ONE layer loop, ``_layers``, and
+  hand it their attention step; the training ``forward`` keeps its own (autograd ops).
 """
 
 from __future__ import annotations
@@ -44,6 +46,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ray_amd.ops import functional as rf
+from ray_amd.ops.graph_lock import CapturedStep
 
 
 @dataclass
@@ -151,21 +154,13 @@ class _GraphedStep:
     inside the graph, so every replay is the step for the next position."""
 
     def __init__(self, model, cache, tok):
-        from ray_amd.ops.graph_lock import CAPTURE_LOCK
-
         self.tok = tok.clone()
-        torch.cuda.synchronize(tok.device)
-        self.graph = torch.cuda.CUDAGraph()
-        with CAPTURE_LOCK, torch.no_grad(), torch.cuda.graph(self.graph):
-            self.logits = model.decode_step(self.tok, cache)
+        self.graph = CapturedStep(lambda: model.decode_step(self.tok, cache), tok.device)
 
     def __call__(self, tok):
-        from ray_amd.ops.graph_lock import CAPTURE_LOCK
-
         self.tok.copy_(tok)
-        with CAPTURE_LOCK:
-            self.graph.replay()
-        return self.logits
+        self.graph.replay()
+        return self.graph.result  # the captured call's logits: a static buffer
 
 
 class _SeededSampler:
@@ -194,37 +189,31 @@ class _SeededSampler:
         self.tok = None  # the sampler's output (inside a capture: the graph's static buffer)
         self.graph = None
 
+    def _draw(self):
+        """Samples a token per row and writes it into column ``col`` of ``out``."""
+        tok = rf.sample_logits(self.logits, self.temperature, self.top_k, self.top_p,
+                               self.seeds, self.cache.lens, done=self.done,
+                               eos_token_id=self.eos, validate=False)
+        self.out.scatter_(1, self.col.expand(self.out.shape[0], 1), tok.unsqueeze(1))
+        return tok
+
     def _step(self):
-        self.tok = rf.sample_logits(self.logits, self.temperature, self.top_k, self.top_p,
-                                    self.seeds, self.cache.lens, done=self.done,
-                                    eos_token_id=self.eos, validate=False)
-        self.out.scatter_(1, self.col.expand(self.out.shape[0], 1), self.tok.unsqueeze(1))
+        self.tok = self._draw()
         self.col += 1
         self.model.decode_step(self.tok, self.cache, out=self.buf)
 
     def draw_last(self):
         """The last token of a call needs no ``decode_step`` after it."""
-        tok = rf.sample_logits(self.logits, self.temperature, self.top_k, self.top_p,
-                               self.seeds, self.cache.lens, done=self.done,
-                               eos_token_id=self.eos, validate=False)
-        self.out.scatter_(1, self.col.expand(self.out.shape[0], 1), tok.unsqueeze(1))
+        self._draw()
 
     def capture(self):
-        from ray_amd.ops.graph_lock import CAPTURE_LOCK
-
-        torch.cuda.synchronize(self.out.device)
-        self.graph = torch.cuda.CUDAGraph()
-        with CAPTURE_LOCK, torch.no_grad(), torch.cuda.graph(self.graph):
-            self._step()
+        self.graph = CapturedStep(self._step, self.out.device)
 
     def __call__(self):
         if self.graph is None:
             self._step()
         else:
-            from ray_amd.ops.graph_lock import CAPTURE_LOCK
-
-            with CAPTURE_LOCK:
-                self.graph.replay()
+            self.graph.replay()
 
 
 def _per_row(name, value, default, B, cast):
@@ -333,11 +322,8 @@ class GPT2(nn.Module):
         lens = torch.as_tensor(lens, device=idx.device).to(torch.int32)
         logits = self._prefill(
             idx, lens, lambda i, qkv: rf.kv_insert(qkv, cache.k[i], cache.v[i], slots, lens))
-        # a slot id outside the cache lands in a spare entry, as kv_insert skips it
-        S = cache.lens.shape[0]
-        sl = slots.long()
-        sl = torch.where((sl >= 0) & (sl < S), sl, S)
-        cache.lens.copy_(torch.cat([cache.lens, cache.lens.new_zeros(1)]).scatter_(0, sl, lens)[:S])
+        # kv_insert skips a slot id outside the cache
+        self._scatter_lens(cache, slots, (slots >= 0) & (slots < cache.lens.shape[0]), lens)
         return logits
 
     @torch.no_grad()
@@ -367,29 +353,50 @@ class GPT2(nn.Module):
         # the padding's positions are clamped into the table; its outputs are dropped
         pos = (base.long().view(Bn, 1) + torch.arange(Tn, device=idx.device)).clamp(
             0, cfg.n_positions - 1)
-        x = self.wte[idx] + self.wpe[pos]
+
+        def attend(i, qkv):
+            y = rf.attn_extend(qkv.view(Bn, Tn, 3, H, hd), cache.k[i], cache.v[i], slots, base,
+                               n_new)
+            return y.reshape(Bn, Tn, cfg.n_embd)
+
+        logits = self._last_logits(self._layers(self.wte[idx] + self.wpe[pos], attend), n_new)
+        # the rows that attn_extend skips
+        sl, bl, nl = slots.long(), base.long(), n_new.long()
+        ok = (sl >= 0) & (sl < cache.lens.shape[0]) & (bl >= 0) & (nl >= 1) & (nl <= Tn) & \
+            (bl + nl <= cache.k.shape[3])
+        self._scatter_lens(cache, sl, ok, (bl + nl).to(torch.int32))
+        return logits
+
+    @staticmethod
+    def _scatter_lens(cache, slots, ok, new_lens):
+        """``cache.lens[slots[b]] = new_lens[b]`` for the rows with ``ok[b]``, IN PLACE (a
+        captured step holds that address); the other rows land in a spare entry."""
+        S = cache.lens.shape[0]
+        sl = torch.where(ok, slots.long(), S)
+        cache.lens.copy_(torch.cat([cache.lens, cache.lens.new_zeros(1)])
+                         .scatter_(0, sl, new_lens)[:S])
+
+    def _layers(self, x, attend):
+        """The transformer layers of the inference paths on the embedded input ``x``
+        [..., C]; returns ``ln_f`` of the result. ``attend(i, qkv)`` takes layer i's c_attn
+        output [..., 3C] and returns the attention output [..., C], the input of c_proj."""
         x, h = self.h[0].ln_1.fork(x)
         for i, blk in enumerate(self.h):
-            qkv = F.linear(h, blk.c_attn_w, blk.c_attn_b).view(Bn, Tn, 3, H, hd)
-            y = rf.attn_extend(qkv, cache.k[i], cache.v[i], slots, base, n_new)
-            a = F.linear(y.reshape(Bn, Tn, cfg.n_embd), blk.c_proj_w)
+            a = F.linear(attend(i, F.linear(h, blk.c_attn_w, blk.c_attn_b)), blk.c_proj_w)
             x, h = rf.residual_layer_norm(a, blk.c_proj_b, x, blk.ln_2.weight, blk.ln_2.bias,
                                           blk.ln_2.eps)
             nxt = self.h[i + 1].ln_1 if i + 1 < len(self.h) else self.ln_f
             m = F.linear(rf.bias_gelu(F.linear(h, blk.c_fc_w), blk.c_fc_b), blk.mlp_proj_w)
             x, h = rf.residual_layer_norm(m, blk.mlp_proj_b, x, nxt.weight, nxt.bias, nxt.eps)
-        last = (n_new.long() - 1).clamp(0, Tn - 1)
-        hl = h[torch.arange(Bn, device=idx.device), last]
-        logits = F.linear(hl, self.wte)[:, : cfg.vocab_size]
-        # a row that attn_extend skipped lands in a spare entry, as in prefill_into
-        S = cache.lens.shape[0]
-        sl, bl, nl = slots.long(), base.long(), n_new.long()
-        ok = (sl >= 0) & (sl < S) & (bl >= 0) & (nl >= 1) & (nl <= Tn) & \
-            (bl + nl <= cache.k.shape[3])
-        sl = torch.where(ok, sl, S)
-        cache.lens.copy_(torch.cat([cache.lens, cache.lens.new_zeros(1)])
-                         .scatter_(0, sl, (bl + nl).to(torch.int32))[:S])
-        return logits
+        return h
+
+    def _last_logits(self, h, n):
+        """Only the last real position ``n[b] - 1`` of each row of ``h`` [B, T, C] meets the
+        tied LM head, [B, C] x [C, V]: returns [B, vocab_size]."""
+        B, T = h.shape[:2]
+        last = (n.long() - 1).clamp(0, T - 1)
+        hl = h[torch.arange(B, device=h.device), last]
+        return F.linear(hl, self.wte)[:, : self.cfg.vocab_size]
 
     def _prefill(self, idx, lens, store):
         """The prompt pass of ``prefill`` / ``prefill_into``: ``store(i, qkv)`` takes layer
@@ -402,22 +409,14 @@ class GPT2(nn.Module):
             # the MFMA flash kernel wants T % 128 == 0; more right padding is as harmless
             Tp = -(-T // 128) * 128
             idx = F.pad(idx, (0, Tp - T))
-        x = rf.embedding(idx, self.wte, self.wpe)
-        x, h = self.h[0].ln_1.fork(x)
-        for i, blk in enumerate(self.h):
-            qkv = F.linear(h, blk.c_attn_w, blk.c_attn_b).view(B, Tp, 3, H, hd)
+
+        def attend(i, qkv):
+            qkv = qkv.view(B, Tp, 3, H, hd)
             store(i, qkv)
-            y = rf.causal_attention_qkv(qkv)
-            a = F.linear(y.reshape(B, Tp, cfg.n_embd), blk.c_proj_w)
-            x, h = rf.residual_layer_norm(a, blk.c_proj_b, x, blk.ln_2.weight, blk.ln_2.bias,
-                                          blk.ln_2.eps)
-            nxt = self.h[i + 1].ln_1 if i + 1 < len(self.h) else self.ln_f
-            m = F.linear(rf.bias_gelu(F.linear(h, blk.c_fc_w), blk.c_fc_b), blk.mlp_proj_w)
-            x, h = rf.residual_layer_norm(m, blk.mlp_proj_b, x, nxt.weight, nxt.bias, nxt.eps)
-        # only the last real position of each row meets the LM head: [B, C] x [C, V]
-        last = (lens.long() - 1).clamp(0, Tp - 1)
-        hl = h[torch.arange(B, device=idx.device), last]
-        return F.linear(hl, self.wte)[:, : cfg.vocab_size]
+            return rf.causal_attention_qkv(qkv).reshape(B, Tp, cfg.n_embd)
+
+        h = self._layers(rf.embedding(idx, self.wte, self.wpe), attend)
+        return self._last_logits(h, lens)
 
     @torch.no_grad()
     def decode_step(self, tok, cache: KVCache, out=None):
@@ -431,17 +430,12 @@ class GPT2(nn.Module):
         B = tok.shape[0]
         H, hd = cfg.n_head, cfg.n_embd // cfg.n_head
         pos = cache.lens.long().clamp(0, cfg.n_positions - 1)
-        x = self.wte[tok] + self.wpe[pos]
-        x, h = self.h[0].ln_1.fork(x)
-        for i, blk in enumerate(self.h):
-            qkv = F.linear(h, blk.c_attn_w, blk.c_attn_b).view(B, 3, H, hd)
-            y = rf.attn_decode(qkv, cache.k[i], cache.v[i], cache.lens)
-            a = F.linear(y.view(B, cfg.n_embd), blk.c_proj_w)
-            x, h = rf.residual_layer_norm(a, blk.c_proj_b, x, blk.ln_2.weight, blk.ln_2.bias,
-                                          blk.ln_2.eps)
-            nxt = self.h[i + 1].ln_1 if i + 1 < len(self.h) else self.ln_f
-            m = F.linear(rf.bias_gelu(F.linear(h, blk.c_fc_w), blk.c_fc_b), blk.mlp_proj_w)
-            x, h = rf.residual_layer_norm(m, blk.mlp_proj_b, x, nxt.weight, nxt.bias, nxt.eps)
+
+        def attend(i, qkv):
+            y = rf.attn_decode(qkv.view(B, 3, H, hd), cache.k[i], cache.v[i], cache.lens)
+            return y.view(B, cfg.n_embd)
+
+        h = self._layers(self.wte[tok] + self.wpe[pos], attend)
         if out is None:
             logits = F.linear(h, self.wte)[:, : cfg.vocab_size]
         else:

@@ -57,6 +57,7 @@ import torch
 
 from ray_amd.models.gpt2 import GPT2, KVCache
 from ray_amd.ops import functional as rf
+from ray_amd.ops.graph_lock import CapturedStep
 
 
 class _Request:
@@ -126,14 +127,9 @@ class GPT2Engine:
         self._next_pid = 0
         self._graph = None
         if graph:
-            from ray_amd.ops.graph_lock import CAPTURE_LOCK
-
             with torch.no_grad():
                 self._device_step()  # every slot idle: warms up what the capture needs
-            torch.cuda.synchronize(dev)
-            self._graph = torch.cuda.CUDAGraph()
-            with CAPTURE_LOCK, torch.no_grad(), torch.cuda.graph(self._graph):
-                self._device_step()
+            self._graph = CapturedStep(self._device_step, dev)
 
     # ------------------------------------------------------------------ the device step
     def _device_step(self):
@@ -148,10 +144,7 @@ class GPT2Engine:
             with torch.no_grad():
                 self._device_step()
         else:
-            from ray_amd.ops.graph_lock import CAPTURE_LOCK
-
-            with CAPTURE_LOCK:
-                self._graph.replay()
+            self._graph.replay()
         self.steps += 1
 
     # ------------------------------------------------------------------ requests

@@ -35,8 +35,8 @@
 //   attn_bwd_dq   : one workgroup per pair of 128-query blocks (forward orientation):
 //                   dQ^T += K^T·dS^T.
 // Softmax statistics are kept in the log2 domain (exp2 with scale·log2e folded).
-// The MFMA, fragment, swizzled-image and tile-register helpers are in attn_mfma.h (shared with
-// attn_extend.hip).
+// The MFMA, fragment, swizzled-image and tile-register helpers and the forward's 64-key tile
+// (fwd_tile) are in attn_mfma.h (shared with attn_extend.hip).
 #include "attn_mfma.h"
 
 #include <type_traits>
@@ -140,16 +140,16 @@ __device__ __forceinline__ void store_rows_lds(bf16_t* img, const f32x16 (&acc)[
 
 // ============================================================================ forward
 // One workgroup covers a pair of 128-query blocks, one after the other (PairedBlock): each
-// wave owns 32 queries of the block (QB = 1 block of 32), two waves per SIMD.
+// wave owns 32 queries of the block, two waves per SIMD. The 64-key tile body is
+// attn_mfma.h's fwd_tile, shared with attn_extend.hip.
 // (Measured and removed: two 32-query blocks per wave at one wave per SIMD, and a 3-waves-
 // per-SIMD register budget — profiles/r5/r5ao, r5at.)
 __global__ __launch_bounds__(256) void attn_fwd_kernel(const bf16_t* __restrict__ qkv,
                                                        bf16_t* __restrict__ out,
                                                        float* __restrict__ lse, int T, int H,
                                                        float sc_log2) {
-  constexpr int QB = 1;
   __shared__ __attribute__((aligned(16))) bf16_t lds[2 * 2 * TILE_ELEMS];  // [buf][K,V]
-  constexpr int QW = 32 * QB;    // queries per wave
+  constexpr int QW = 32;         // queries per wave
   constexpr int QBLK = 4 * QW;   // queries per workgroup
   const int nqb = T / QBLK;
   const PairedBlock pb(xcd_block(blockIdx.x, gridDim.x), nqb);
@@ -163,32 +163,26 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const bf16_t* __restrict_
   // per-block state: the heavy block nqb-1-i first, then (second pass) the light block i
   int qb = nqb - 1 - pb.i;
   int q0, wave_qmin, wave_qmax, ntiles;
-  int qrow[QB];
-  bf16x8_t qf[QB][4];
-  f32x16 o[QB][2];
-  float m_run[QB], l_run[QB];
+  int qrow;
+  bf16x8_t qf[4];
+  f32x16 o[2];
+  float m_run, l_run;
   auto set_block = [&]() __attribute__((always_inline)) {
     q0 = qb * QBLK;
     wave_qmin = q0 + QW * w;
     wave_qmax = wave_qmin + QW - 1;
     ntiles = (q0 + QBLK) / 64;
-#pragma unroll
-    for (int j = 0; j < QB; ++j) {
-      qrow[j] = wave_qmin + 32 * j + r;
-      o[j][0] = f32x16{};
-      o[j][1] = f32x16{};
-      m_run[j] = -INFINITY;
-      l_run[j] = 0.f;
-    }
+    qrow = wave_qmin + r;
+    o[0] = f32x16{};
+    o[1] = f32x16{};
+    m_run = -INFINITY;
+    l_run = 0.f;
   };
   // ln: the lane id (the seam passes opaque_lane, which pins the loads there)
-  auto load_q = [&](bf16x8_t (&x)[QB][4], int blk, int ln) __attribute__((always_inline)) {
+  auto load_q = [&](bf16x8_t (&x)[4], int blk, int ln) __attribute__((always_inline)) {
 #pragma unroll
-    for (int j = 0; j < QB; ++j)
-#pragma unroll
-      for (int kk = 0; kk < 4; ++kk)
-        x[j][kk] = ld8(base + (long)(blk * QBLK + QW * w + 32 * j + (ln & 31)) * tok + 16 * kk +
-                       8 * (ln >> 5));
+    for (int kk = 0; kk < 4; ++kk)
+      x[kk] = ld8(base + (long)(blk * QBLK + QW * w + (ln & 31)) * tok + 16 * kk + 8 * (ln >> 5));
   };
   set_block();
   load_q(qf, qb, lane);
@@ -207,76 +201,10 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const bf16_t* __restrict_
     tile_store(x.k, d);
     tile_store(x.v, d + TILE_ELEMS);
   };
-  auto body = [&](int t, auto diag_c) __attribute__((always_inline)) {
-    constexpr bool diag = decltype(diag_c)::value;
+  auto body = [&](int t, auto diag_c) __attribute__((always_inline)) {  // diag: mask keys > query
     const bf16_t* Ks = lds + (t & 1) * 2 * TILE_ELEMS;
-    const bf16_t* Vs = Ks + TILE_ELEMS;
-    const int kv0 = t * 64;
-    f32x16 st[QB][2];
-#pragma unroll
-    for (int kt = 0; kt < 2; ++kt) {
-#pragma unroll
-      for (int j = 0; j < QB; ++j) st[j][kt] = f32x16{};
-#pragma unroll
-      for (int kk = 0; kk < 4; ++kk) {
-        const bf16x8_t kfrag = ld8(Ks + 2048 * kt + lo.row[kk]);
-#pragma unroll
-        for (int j = 0; j < QB; ++j) st[j][kt] = mfma32(kfrag, qf[j][kk], st[j][kt]);
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < QB; ++j) {
-      if (diag) {  // diagonal tile: mask keys > query
-#pragma unroll
-        for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-          for (int i = 0; i < 16; ++i)
-            if (kv0 + 32 * kt + crow(i, hh) > qrow[j]) st[j][kt][i] = -INFINITY;
-      }
-      float mt = st[j][0][0];
-#pragma unroll
-      for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) mt = fmaxf(mt, st[j][kt][i]);
-      mt = half_max(mt) * sc_log2;
-      // Lazy rescaling: the running max moves (and O / l are rescaled) only when some
-      // query's tile max exceeds it by more than 8 (log2 units). Otherwise the stale max
-      // stays, p <= 2^8 — exact in fp32, and the final O / l is unchanged: the common tile
-      // skips the 32 multiplies of the O rescale and the exp of alpha. A wave-uniform
-      // branch (the first tile always takes it: m_run = -inf). A tile entirely above the
-      // diagonal for this block (QB 2, first block) has mt = -inf and changes nothing.
-      if (__builtin_amdgcn_ballot_w64(mt > m_run[j] + 8.f)) {
-        const float m_new = fmaxf(m_run[j], mt);
-        const float alpha = fast_exp2(m_run[j] - m_new);
-        l_run[j] *= alpha;
-        m_run[j] = m_new;
-#pragma unroll
-        for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-          for (int i = 0; i < 16; ++i) o[j][dt][i] *= alpha;
-      }
-      float ls = 0.f;
-#pragma unroll
-      for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-          const float p = fast_exp2(fmaf(st[j][kt][i], sc_log2, -m_run[j]));
-          st[j][kt][i] = p;
-          ls += p;
-        }
-      l_run[j] += half_sum(ls);
-    }
-#pragma unroll
-    for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-#pragma unroll
-        for (int dt = 0; dt < 2; ++dt) {
-          const bf16x8_t vfrag = tr_frag(Vs, lo, 32 * kt + 16 * s, dt);
-#pragma unroll
-          for (int j = 0; j < QB; ++j) o[j][dt] = mfma32(vfrag, acc_frag(st[j][kt], s), o[j][dt]);
-        }
-      }
+    fwd_tile<decltype(diag_c)::value>(Ks, Ks + TILE_ELEMS, lo, qf, t * 64, qrow, hh, sc_log2, o,
+                                      m_run, l_run);
   };
   auto compute = [&](int t) __attribute__((always_inline)) {
     const int kv0 = t * 64;
@@ -313,15 +241,11 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const bf16_t* __restrict_
     // The K/V images are dead after the last tile's barrier: O leaves through buffer 1. The
     // next block writes buffer 0 first and buffer 1 only after its first barrier, by which
     // every wave has read its staging region back.
-    static_assert(4 * QB * 2048 <= 2 * TILE_ELEMS, "O staging must fit one tile buffer");
-#pragma unroll
-    for (int j = 0; j < QB; ++j) {
-      const float inv = 1.f / l_run[j];
-      store_rows_lds(lds + 2 * TILE_ELEMS + (w * QB + j) * 2048, o[j], inv,
-                     out + ((long)b * T + wave_qmin + 32 * j) * C + h * HD, C,
-                     opaque_lane(lane));
-      if (hh == 0) lse[(long)bh * T + qrow[j]] = m_run[j] + log2f(l_run[j]);
-    }
+    static_assert(4 * 2048 <= 2 * TILE_ELEMS, "O staging must fit one tile buffer");
+    const float inv = 1.f / l_run;
+    store_rows_lds(lds + 2 * TILE_ELEMS + w * 2048, o, inv,
+                   out + ((long)b * T + wave_qmin) * C + h * HD, C, opaque_lane(lane));
+    if (hh == 0) lse[(long)bh * T + qrow] = m_run + log2f(l_run);
     if (!more) break;
     qb = pb.i;
     set_block();

@@ -15,13 +15,15 @@
 // read, capturable. Slots are distinct among the active rows (the caller's contract).
 //
 // Two launches on one stream (the UNFUSED form): kv_append_kernel, which is kv_slots.hip's
-// kv_insert_kernel with a per-row position offset, then attn_extend_kernel, which reads every
+// kv_insert_kernel with a per-row position offset (both move their rows with kv_rows.h's
+// kv_move_rows), then attn_extend_kernel, which reads every
 // key, old and new, from the cache. So the tile loop has ONE K/V source, and no workgroup
 // reads a cache position that another workgroup of its own launch is writing. (Fused, the
 // new keys would have to come from qkv_new, at another row stride, in every tile past
 // `base`: a second addressing mode in the hot loop to save one ~2 us launch.)
 //
-// attn_extend_kernel is the forward of attn.hip on another address map: S^T = K.Q^T with
+// attn_extend_kernel is the forward of attn.hip on another address map, and runs the same
+// tile body (attn_mfma.h's fwd_tile, so the two cannot drift apart): S^T = K.Q^T with
 // v_mfma_f32_32x32x16_bf16, so a lane owns one query and the online softmax is lane-local in
 // the log2 domain (lazy rescaling included); P^T's accumulators are the B operand of
 // O^T = V^T.P^T; K/V tiles of 64 keys in the swizzled LDS image, double buffered, two tiles
@@ -52,6 +54,7 @@
 // Bn = 1, twelve workgroups each walking its tiles alone. So a 32- or 64-query block with
 // the waves splitting the keys and merging through LDS was not built.
 #include "attn_mfma.h"
+#include "kv_rows.h"
 
 #include <type_traits>
 
@@ -77,40 +80,19 @@ __device__ __forceinline__ ExtendRow extend_row(const int* slots, const int* bas
 
 // ---------------------------------------------------------------- append
 // kv_slots.hip's kv_insert_kernel with the destination shifted by base[b]: a workgroup owns
-// 64 new positions of one (b, h), K and V, 8 lanes x 16 B per row, four loads in flight
-// before the first store, no branch after the row test (a lane past the end moves position
-// n - 1 again, the same bytes its own lane writes), no LDS.
-constexpr int kAppThreads = 256;
-constexpr int kAppRows = kAppThreads / 8;
-constexpr int kAppPasses = 2;
-constexpr int kAppBlock = kAppRows * kAppPasses;
-
-__global__ __launch_bounds__(kAppThreads) void kv_append_kernel(
+// 64 new positions of one (b, h), K and V, and moves them with kv_rows.h's kv_move_rows.
+__global__ __launch_bounds__(kKvThreads) void kv_append_kernel(
     const bf16_t* __restrict__ qkv, bf16_t* __restrict__ kc, bf16_t* __restrict__ vc,
     const int* __restrict__ slots, const int* __restrict__ base, const int* __restrict__ n_new,
     int Tn, int H, int S, int Tmax) {
   const int b = blockIdx.z, h = blockIdx.y;
   const ExtendRow row = extend_row(slots, base, n_new, b, S, Tn, Tmax);
-  const int t0 = blockIdx.x * kAppBlock;
-  if (t0 >= row.n) return;
-  const int r = threadIdx.x >> 3, c = threadIdx.x & 7;
-  const long tstride = 3L * H * kD;
+  const int t0 = blockIdx.x * kKvBlockRows;
+  if (t0 >= row.n) return;  // (n <= Tn and base + n <= Tmax: real positions of both tensors)
+  const int c = threadIdx.x & 7;
   const bf16_t* src = qkv + ((long)b * Tn * 3 + 1) * H * kD + (long)h * kD + c * 8;
   const long dst0 = (((long)row.slot * H + h) * Tmax + row.base) * kD + c * 8;
-  uint4 kk[kAppPasses], vv[kAppPasses];
-#pragma unroll
-  for (int u = 0; u < kAppPasses; ++u) {
-    const int t = min(t0 + u * kAppRows + r, row.n - 1);
-    const bf16_t* p = src + (long)t * tstride;
-    kk[u] = *reinterpret_cast<const uint4*>(p);
-    vv[u] = *reinterpret_cast<const uint4*>(p + (long)H * kD);
-  }
-#pragma unroll
-  for (int u = 0; u < kAppPasses; ++u) {
-    const int t = min(t0 + u * kAppRows + r, row.n - 1);
-    *reinterpret_cast<uint4*>(kc + dst0 + (long)t * kD) = kk[u];
-    *reinterpret_cast<uint4*>(vc + dst0 + (long)t * kD) = vv[u];
-  }
+  kv_move_rows(src, src + (long)H * kD, 3L * H * kD, kc + dst0, vc + dst0, t0, row.n);
 }
 
 // ---------------------------------------------------------------- attention
@@ -180,62 +162,14 @@ __global__ __launch_bounds__(256) void attn_extend_kernel(
     tile_store(x.k, d);
     tile_store(x.v, d + kTile);
   };
+  // The diagonal tiles mask keys > qpos, the clamped duplicates included. Unlike attn.hip, a
+  // lane's tile can be masked whole (its qpos below the tile, a later query of the wave
+  // inside it): in fwd_tile's lazy rescaling mt = -inf, m_new = m_run, alpha = 1, p = 0.
+  // Tile 0 holds key 0 for every lane, so m_run is finite from then on.
   auto body = [&](int t, auto diag_c) __attribute__((always_inline)) {
-    constexpr bool diag = decltype(diag_c)::value;
     const bf16_t* Ks = lds + (t & 1) * 2 * kTile;
-    const bf16_t* Vs = Ks + kTile;
-    const int kv0 = t * 64;
-    f32x16 st[2];
-#pragma unroll
-    for (int kt = 0; kt < 2; ++kt) {
-      st[kt] = f32x16{};
-#pragma unroll
-      for (int kk = 0; kk < 4; ++kk)
-        st[kt] = mfma32(ld8(Ks + 2048 * kt + lo.row[kk]), qf[kk], st[kt]);
-    }
-    if (diag) {  // a select, never an add: keys > qpos, the clamped duplicates included
-#pragma unroll
-      for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-        for (int i = 0; i < 16; ++i)
-          if (kv0 + 32 * kt + crow(i, hh) > qpos) st[kt][i] = -INFINITY;
-    }
-    float mt = st[0][0];
-#pragma unroll
-    for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) mt = fmaxf(mt, st[kt][i]);
-    mt = half_max(mt) * sc_log2;
-    // Lazy rescaling as attn.hip. Unlike there, a lane's tile can be masked whole (its qpos
-    // below the tile, a later query of the wave inside it): mt = -inf, m_new = m_run,
-    // alpha = 1, p = 0. Tile 0 holds key 0 for every lane, so m_run is finite from then on.
-    if (__builtin_amdgcn_ballot_w64(mt > m_run + 8.f)) {
-      const float m_new = fmaxf(m_run, mt);
-      const float alpha = fast_exp2(m_run - m_new);
-      l_run *= alpha;
-      m_run = m_new;
-#pragma unroll
-      for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) o[dt][i] *= alpha;
-    }
-    float ls = 0.f;
-#pragma unroll
-    for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        const float p = fast_exp2(fmaf(st[kt][i], sc_log2, -m_run));
-        st[kt][i] = p;
-        ls += p;
-      }
-    l_run += half_sum(ls);
-#pragma unroll
-    for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-      for (int s = 0; s < 2; ++s)
-#pragma unroll
-        for (int dt = 0; dt < 2; ++dt)
-          o[dt] = mfma32(tr_frag(Vs, lo, 32 * kt + 16 * s, dt), acc_frag(st[kt], s), o[dt]);
+    fwd_tile<decltype(diag_c)::value>(Ks, Ks + kTile, lo, qf, t * 64, qpos, hh, sc_log2, o,
+                                      m_run, l_run);
   };
   auto compute = [&](int t) __attribute__((always_inline)) {
     const int kv0 = t * 64;
@@ -305,8 +239,8 @@ RA_EXPORT int ra_attn_extend(const void* qkv_new, void* k_cache, void* v_cache, 
   if ((((uintptr_t)qkv_new | (uintptr_t)k_cache | (uintptr_t)v_cache | (uintptr_t)out) & 15) ||
       slots == nullptr || base == nullptr || n_new == nullptr)
     return hipErrorInvalidValue;
-  hipLaunchKernelGGL(kv_append_kernel, dim3((Tn + kAppBlock - 1) / kAppBlock, H, Bn),
-                     dim3(kAppThreads), 0, st, (const bf16_t*)qkv_new, (bf16_t*)k_cache,
+  hipLaunchKernelGGL(kv_append_kernel, dim3((Tn + kKvBlockRows - 1) / kKvBlockRows, H, Bn),
+                     dim3(kKvThreads), 0, st, (const bf16_t*)qkv_new, (bf16_t*)k_cache,
                      (bf16_t*)v_cache, slots, base, n_new, Tn, H, S, Tmax);
   hipLaunchKernelGGL(attn_extend_kernel, dim3((Tn + kQBlk - 1) / kQBlk, H, Bn), dim3(256), 0, st,
                      (const bf16_t*)qkv_new, (const bf16_t*)k_cache, (const bf16_t*)v_cache, slots,

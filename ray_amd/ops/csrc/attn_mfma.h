@@ -1,8 +1,8 @@
 // Building blocks shared by the head_dim-64 MFMA attention kernels (attn.hip,
 // attn_extend.hip): the 32x32x16 bf16 MFMA and its fragment helpers, the swizzled LDS image
-// of a [rows][64] bf16 tile and its lane-constant read offsets, tile registers and the
-// wave-private LDS ordering of the epilogues. See attn.hip's header for the orientation and
-// the bank-conflict argument.
+// of a [rows][64] bf16 tile and its lane-constant read offsets, the forward's 64-key tile
+// (fwd_tile), tile registers and the wave-private LDS ordering of the epilogues. See
+// attn.hip's header for the orientation and the bank-conflict argument.
 #pragma once
 #include "common.h"
 
@@ -85,6 +85,73 @@ struct LaneOffs {
 // (the acc_frag k order), column 32dt + (lane&31)
 __device__ __forceinline__ bf16x8_t tr_frag(const bf16_t* img, const LaneOffs& lo, int kb, int dt) {
   return cat44(tr4(img + 64 * kb + lo.tr[0][dt]), tr4(img + 64 * kb + lo.tr[1][dt]));
+}
+
+// ---------------------------------------------------------------- the forward's tile
+// One 64-key tile of the forward (attn_fwd_kernel, attn_extend_kernel) for a wave's 32
+// queries: S^T = K.Q^T from the K image `Ks`, the online softmax in the log2 domain, then
+// O^T += V^T.P^T from the V image `Vs`. `qf`: the lane's Q fragments; `kv0`: the tile's first
+// key; `qpos`: the last key this lane's query attends to (read on a kDiag tile only, which
+// masks the keys past it with a select, never an add); `o`, `m_run`, `l_run`: the lane's
+// running output, max and sum.
+template <bool kDiag>
+__device__ __forceinline__ void fwd_tile(const bf16_t* Ks, const bf16_t* Vs, const LaneOffs& lo,
+                                         const bf16x8_t (&qf)[4], int kv0, int qpos, int hh,
+                                         float sc_log2, f32x16 (&o)[2], float& m_run,
+                                         float& l_run) {
+  f32x16 st[2];
+#pragma unroll
+  for (int kt = 0; kt < 2; ++kt) {
+    st[kt] = f32x16{};
+#pragma unroll
+    for (int kk = 0; kk < 4; ++kk)
+      st[kt] = mfma32(ld8(Ks + 2048 * kt + lo.row[kk]), qf[kk], st[kt]);
+  }
+  if (kDiag) {
+#pragma unroll
+    for (int kt = 0; kt < 2; ++kt)
+#pragma unroll
+      for (int i = 0; i < 16; ++i)
+        if (kv0 + 32 * kt + crow(i, hh) > qpos) st[kt][i] = -INFINITY;
+  }
+  float mt = st[0][0];
+#pragma unroll
+  for (int kt = 0; kt < 2; ++kt)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) mt = fmaxf(mt, st[kt][i]);
+  mt = half_max(mt) * sc_log2;
+  // Lazy rescaling: the running max moves (and O / l are rescaled) only when some query's
+  // tile max exceeds it by more than 8 (log2 units). Otherwise the stale max stays,
+  // p <= 2^8 — exact in fp32, and the final O / l is unchanged: the common tile skips the 32
+  // multiplies of the O rescale and the exp of alpha. A wave-uniform branch (the first tile
+  // always takes it: m_run = -inf).
+  if (__builtin_amdgcn_ballot_w64(mt > m_run + 8.f)) {
+    const float m_new = fmaxf(m_run, mt);
+    const float alpha = fast_exp2(m_run - m_new);
+    l_run *= alpha;
+    m_run = m_new;
+#pragma unroll
+    for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+      for (int i = 0; i < 16; ++i) o[dt][i] *= alpha;
+  }
+  float ls = 0.f;
+#pragma unroll
+  for (int kt = 0; kt < 2; ++kt)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      const float p = fast_exp2(fmaf(st[kt][i], sc_log2, -m_run));
+      st[kt][i] = p;
+      ls += p;
+    }
+  l_run += half_sum(ls);
+#pragma unroll
+  for (int kt = 0; kt < 2; ++kt)
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+      for (int dt = 0; dt < 2; ++dt)
+        o[dt] = mfma32(tr_frag(Vs, lo, 32 * kt + 16 * s, dt), acc_frag(st[kt], s), o[dt]);
 }
 
 // ---------------------------------------------------------------- tile staging

@@ -16,9 +16,10 @@
 // else is written. Layout as attn_decode.hip: a 128-byte row is 8 lanes x 16 B, and for a
 // fixed (b, h) consecutive t are contiguous in the cache, so one wave-wide store writes
 // 1 KiB; the reads are whole 128-byte segments at stride 3 * H * 128 B. Grid (ceil(n / 64),
-// H, Bn) with n = min(Tp, Tmax); a workgroup owns 64 positions of one (b, h), K and V, four
-// 16-byte loads per lane in flight before the first store; workgroups past lens[b] exit
-// after reading it. No LDS.
+// H, Bn) with n = min(Tp, Tmax); a workgroup owns 64 positions of one (b, h), K and V, and
+// moves them with kv_rows.h's kv_move_rows (shared with ra_kv_copy and attn_extend.hip's
+// append): four 16-byte loads per lane in flight before the first store; workgroups past
+// lens[b] exit after reading it. No LDS.
 //
 // ra_kv_copy: the shared-prefix path. Copies cached rows from one cache to another, all
 // layers, K and V, in one launch.
@@ -30,9 +31,8 @@
 // min(Tsrc, Tdst), every layer l, head h and t < lens[b]:
 // dst[l, dst_rows[b], h, t, :] = src[l, src_rows[b], h, t, :]; any other b is skipped and
 // nothing else is written. Built as ra_kv_insert: grid (ceil(n / 64), L * H, Bn) with
-// n = min(Tsrc, Tdst), a workgroup owns 64 positions of one (l, h, b), K and V, four 16-byte
-// loads per lane in flight before the first store (here both sides are 1 KiB contiguous per
-// wave instruction), no branch after the row-length test, no LDS.
+// n = min(Tsrc, Tdst), a workgroup owns 64 positions of one (l, h, b), K and V, the same
+// kv_move_rows (here both sides are 1 KiB contiguous per wave instruction), no LDS.
 //
 // ra_slot_advance: the per-token path, after the sampler, one thread per slot.
 //
@@ -46,76 +46,42 @@
 // call: decode_step adds 1 to every lens each step, and the re-pin keeps an idle slot from
 // ever walking back into [0, Tmax). A slot retired here is already inactive for the
 // decode_step that follows.
-#include "common.h"
+#include "kv_rows.h"
 
 namespace {
 
 constexpr int kD = 64;
-constexpr int kThreads = 256;
-constexpr int kRowsPerPass = kThreads / 8;  // 32 positions: one 16-byte lane chunk each
-constexpr int kPasses = 2;
-constexpr int kBlockRows = kRowsPerPass * kPasses;
 constexpr int kSlotInactive = -(1 << 30);
 
-__global__ __launch_bounds__(kThreads) void kv_insert_kernel(
+__global__ __launch_bounds__(kKvThreads) void kv_insert_kernel(
     const bf16_t* __restrict__ qkv, bf16_t* __restrict__ kc, bf16_t* __restrict__ vc,
     const int* __restrict__ slots, const int* __restrict__ lens, int Tp, int H, int S, int Tmax) {
   const int b = blockIdx.z, h = blockIdx.y;
   const int slot = slots[b];
   if (slot < 0 || slot >= S) return;
-  const int len = min(lens[b], min(Tp, Tmax));
-  const int t0 = blockIdx.x * kBlockRows;
+  const int len = min(lens[b], min(Tp, Tmax));  // real positions of both tensors
+  const int t0 = blockIdx.x * kKvBlockRows;
   if (t0 >= len) return;
-  const int r = threadIdx.x >> 3, c = threadIdx.x & 7;
-  const long tstride = 3L * H * kD;  // elements between positions of one (b, which, h)
+  const int c = threadIdx.x & 7;
+  // qkv[b, 0, 1, h] (K; V is H * kD further) and the cache's [slot, h, 0]
   const bf16_t* src = qkv + ((long)b * Tp * 3 + 1) * H * kD + (long)h * kD + c * 8;
   const long dst0 = (((long)slot * H + h) * Tmax) * kD + c * 8;
-  // No branch from here on, so all four loads are in flight before the first store: a lane
-  // past the row's end moves position len - 1 instead (t0 < len <= min(Tp, Tmax), so that
-  // is a real position of both tensors), the same bytes that position's own lane writes.
-  uint4 kk[kPasses], vv[kPasses];
-#pragma unroll
-  for (int u = 0; u < kPasses; ++u) {
-    const int t = min(t0 + u * kRowsPerPass + r, len - 1);
-    const bf16_t* p = src + (long)t * tstride;
-    kk[u] = *reinterpret_cast<const uint4*>(p);
-    vv[u] = *reinterpret_cast<const uint4*>(p + (long)H * kD);
-  }
-#pragma unroll
-  for (int u = 0; u < kPasses; ++u) {
-    const int t = min(t0 + u * kRowsPerPass + r, len - 1);
-    *reinterpret_cast<uint4*>(kc + dst0 + (long)t * kD) = kk[u];
-    *reinterpret_cast<uint4*>(vc + dst0 + (long)t * kD) = vv[u];
-  }
+  kv_move_rows(src, src + (long)H * kD, 3L * H * kD, kc + dst0, vc + dst0, t0, len);
 }
 
-__global__ __launch_bounds__(kThreads) void kv_copy_kernel(
+__global__ __launch_bounds__(kKvThreads) void kv_copy_kernel(
     const bf16_t* __restrict__ sk, const bf16_t* __restrict__ sv, bf16_t* __restrict__ dk,
     bf16_t* __restrict__ dv, const int* __restrict__ src_rows, const int* __restrict__ dst_rows,
     const int* __restrict__ lens, int H, int P, int Tsrc, int S, int Tdst) {
   const int b = blockIdx.z, l = blockIdx.y / H, h = blockIdx.y % H;
   const int sr = src_rows[b], dr = dst_rows[b], len = lens[b];
   if (sr < 0 || sr >= P || dr < 0 || dr >= S || len < 0 || len > min(Tsrc, Tdst)) return;
-  const int t0 = blockIdx.x * kBlockRows;
-  if (t0 >= len) return;
-  const int r = threadIdx.x >> 3, c = threadIdx.x & 7;
+  const int t0 = blockIdx.x * kKvBlockRows;
+  if (t0 >= len) return;  // (len <= min(Tsrc, Tdst): real positions of both caches)
+  const int c = threadIdx.x & 7;
   const long src0 = ((((long)l * P + sr) * H + h) * Tsrc) * kD + c * 8;
   const long dst0 = ((((long)l * S + dr) * H + h) * Tdst) * kD + c * 8;
-  // As kv_insert_kernel: no branch from here on, a lane past the row's end moves position
-  // len - 1 again (t0 < len <= min(Tsrc, Tdst): a real position of both caches).
-  uint4 kk[kPasses], vv[kPasses];
-#pragma unroll
-  for (int u = 0; u < kPasses; ++u) {
-    const int t = min(t0 + u * kRowsPerPass + r, len - 1);
-    kk[u] = *reinterpret_cast<const uint4*>(sk + src0 + (long)t * kD);
-    vv[u] = *reinterpret_cast<const uint4*>(sv + src0 + (long)t * kD);
-  }
-#pragma unroll
-  for (int u = 0; u < kPasses; ++u) {
-    const int t = min(t0 + u * kRowsPerPass + r, len - 1);
-    *reinterpret_cast<uint4*>(dk + dst0 + (long)t * kD) = kk[u];
-    *reinterpret_cast<uint4*>(dv + dst0 + (long)t * kD) = vv[u];
-  }
+  kv_move_rows(sk + src0, sv + src0, kD, dk + dst0, dv + dst0, t0, len);
 }
 
 __global__ __launch_bounds__(64) void slot_advance_kernel(
@@ -154,8 +120,8 @@ RA_EXPORT int ra_kv_insert(const void* qkv, void* k_cache, void* v_cache, const 
       lens == nullptr)
     return hipErrorInvalidValue;
   const int n = Tp < Tmax ? Tp : Tmax;
-  hipLaunchKernelGGL(kv_insert_kernel, dim3((n + kBlockRows - 1) / kBlockRows, H, Bn),
-                     dim3(kThreads), 0, st, (const bf16_t*)qkv, (bf16_t*)k_cache,
+  hipLaunchKernelGGL(kv_insert_kernel, dim3((n + kKvBlockRows - 1) / kKvBlockRows, H, Bn),
+                     dim3(kKvThreads), 0, st, (const bf16_t*)qkv, (bf16_t*)k_cache,
                      (bf16_t*)v_cache, slots, lens, Tp, H, S, Tmax);
   return hipGetLastError();
 }
@@ -173,8 +139,8 @@ RA_EXPORT int ra_kv_copy(const void* src_k, const void* src_v, void* dst_k, void
       src_rows == nullptr || dst_rows == nullptr || lens == nullptr)
     return hipErrorInvalidValue;
   const int n = Tsrc < Tdst ? Tsrc : Tdst;
-  hipLaunchKernelGGL(kv_copy_kernel, dim3((n + kBlockRows - 1) / kBlockRows, L * H, Bn),
-                     dim3(kThreads), 0, st, (const bf16_t*)src_k, (const bf16_t*)src_v,
+  hipLaunchKernelGGL(kv_copy_kernel, dim3((n + kKvBlockRows - 1) / kKvBlockRows, L * H, Bn),
+                     dim3(kKvThreads), 0, st, (const bf16_t*)src_k, (const bf16_t*)src_v,
                      (bf16_t*)dst_k, (bf16_t*)dst_v, src_rows, dst_rows, lens, H, P, Tsrc, S, Tdst);
   return hipGetLastError();
 }

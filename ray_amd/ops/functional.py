@@ -654,6 +654,24 @@ def _int_vec(name, op, t, n, like, dtype=torch.int32):
         raise ValueError(f"{op}: {name} must be a {dtype} tensor of shape [{n}] on {like.device}")
 
 
+def _check_qkv_caches(op, qkv, k_cache, v_cache):
+    """``qkv`` [Bn, T, 3, H, D] against the caches [S, H, Tmax, D], all non-empty, on one
+    device, the caches of one dtype: returns (Bn, T, H, D, S, Tmax)."""
+    if qkv.dim() != 5 or qkv.shape[2] != 3:
+        raise ValueError(f"{op}: qkv must be [Bn, T, 3, H, D], got {tuple(qkv.shape)}")
+    Bn, T, _, H, D = qkv.shape
+    if k_cache.shape != v_cache.shape or k_cache.dim() != 4 or k_cache.shape[1] != H or \
+            k_cache.shape[3] != D:
+        raise ValueError(f"{op}: the caches must be [S, H, Tmax, D]")
+    S, _, Tmax, _ = k_cache.shape
+    if min(Bn, T, H, S, Tmax) < 1:
+        raise ValueError(f"{op}: empty qkv or cache")
+    if k_cache.dtype != v_cache.dtype or k_cache.device != qkv.device or \
+            v_cache.device != qkv.device:
+        raise ValueError(f"{op}: qkv and the caches must share a device, the caches a dtype")
+    return Bn, T, H, D, S, Tmax
+
+
 def kv_insert(qkv, k_cache, v_cache, slots, lens):
     """Moves one layer's prefill K/V (``qkv`` [Bn, Tp, 3, H, D], the packed c_attn output
     of the right-padded prompts) into slots of a wider cache: for every row b with
@@ -665,18 +683,7 @@ def kv_insert(qkv, k_cache, v_cache, slots, lens):
 
     HIP kernel for bf16, D == 64 GPU tensors; CPU tensors, other dtypes and other head
     sizes use the plain-torch reference."""
-    if qkv.dim() != 5 or qkv.shape[2] != 3:
-        raise ValueError(f"kv_insert: qkv must be [Bn, Tp, 3, H, D], got {tuple(qkv.shape)}")
-    Bn, Tp, _, H, D = qkv.shape
-    if k_cache.shape != v_cache.shape or k_cache.dim() != 4 or k_cache.shape[1] != H or \
-            k_cache.shape[3] != D:
-        raise ValueError("kv_insert: the caches must be [S, H, Tmax, D]")
-    S, _, Tmax, _ = k_cache.shape
-    if min(Bn, Tp, H, S, Tmax) < 1:
-        raise ValueError("kv_insert: empty qkv or cache")
-    if k_cache.dtype != v_cache.dtype or k_cache.device != qkv.device or \
-            v_cache.device != qkv.device:
-        raise ValueError("kv_insert: qkv and the caches must share a device, the caches a dtype")
+    Bn, Tp, H, D, S, Tmax = _check_qkv_caches("kv_insert", qkv, k_cache, v_cache)
     _int_vec("slots", "kv_insert", slots, Bn, qkv)
     _int_vec("lens", "kv_insert", lens, Bn, qkv)
     if not (_hip(qkv) and qkv.dtype == torch.bfloat16 and D == 64
@@ -711,20 +718,7 @@ def attn_extend(qkv_new, k_cache, v_cache, slots, base, n_new, scale=None):
     if qkv_new.requires_grad or k_cache.requires_grad or v_cache.requires_grad:
         raise RuntimeError("attn_extend is an inference op: run it under torch.no_grad() on "
                            "tensors that do not require grad")
-    if qkv_new.dim() != 5 or qkv_new.shape[2] != 3:
-        raise ValueError(f"attn_extend: qkv_new must be [Bn, Tn, 3, H, D], got "
-                         f"{tuple(qkv_new.shape)}")
-    Bn, Tn, _, H, D = qkv_new.shape
-    if k_cache.shape != v_cache.shape or k_cache.dim() != 4 or k_cache.shape[1] != H or \
-            k_cache.shape[3] != D:
-        raise ValueError("attn_extend: the caches must be [S, H, Tmax, D]")
-    S, _, Tmax, _ = k_cache.shape
-    if min(Bn, Tn, H, S, Tmax) < 1:
-        raise ValueError("attn_extend: empty qkv_new or cache")
-    if k_cache.dtype != v_cache.dtype or k_cache.device != qkv_new.device or \
-            v_cache.device != qkv_new.device:
-        raise ValueError("attn_extend: qkv_new and the caches must share a device, the caches "
-                         "a dtype")
+    Bn, Tn, H, D, S, Tmax = _check_qkv_caches("attn_extend", qkv_new, k_cache, v_cache)
     for name, t in (("slots", slots), ("base", base), ("n_new", n_new)):
         _int_vec(name, "attn_extend", t, Bn, qkv_new)
     if scale is None:

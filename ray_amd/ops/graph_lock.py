@@ -5,4 +5,23 @@ replaying its inference graph (rllib/env/policy_server.py) — take turns throug
 
 import threading
 
+import torch
+
 CAPTURE_LOCK = threading.RLock()
+
+
+class CapturedStep:
+    """``fn()`` recorded once in a HIP graph (one stream, no parallel branches) after a
+    device synchronisation, under ``CAPTURE_LOCK`` and ``torch.no_grad()``; ``result`` is
+    what the recorded call returned (static buffers), ``replay`` runs the graph under the
+    lock. Whatever the capture needs warmed up, the caller has run eagerly before."""
+
+    def __init__(self, fn, device):
+        torch.cuda.synchronize(device)
+        self.graph = torch.cuda.CUDAGraph()
+        with CAPTURE_LOCK, torch.no_grad(), torch.cuda.graph(self.graph):
+            self.result = fn()
+
+    def replay(self):
+        with CAPTURE_LOCK:
+            self.graph.replay()

@@ -36,6 +36,7 @@ def _bits(shape, g):
     ((3, 128, 2, 5, 160), [4, 0, 2], [1, 37, 128]),
     ((4, 40, 2, 3, 24), [1, -1, 3, 0], [40, 5, 7, 0]),  # clamp to Tmax, two skipped rows
     ((2, 256, 12, 2, 256), [1, 0], [256, 200]),
+    ((4, 130, 1, 4, 130), [3, 1, 0, 2], [63, 64, 65, 129]),  # the mover's 64-row block edge
 ])
 def test_kv_insert_bitwise(cuda_device, shape, slots, lens):
     Bn, Tp, H, S, Tmax = shape
