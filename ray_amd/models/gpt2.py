@@ -153,9 +153,10 @@ class _GraphedStep:
     static token and logits buffers; ``cache.lens`` lives on the device and is advanced
     inside the graph, so every replay is the step for the next position."""
 
-    def __init__(self, model, cache, tok):
+    def __init__(self, model, cache, tok, adapters=None):
         self.tok = tok.clone()
-        self.graph = CapturedStep(lambda: model.decode_step(self.tok, cache), tok.device)
+        self.graph = CapturedStep(
+            lambda: model.decode_step(self.tok, cache, adapters=adapters), tok.device)
 
     def __call__(self, tok):
         self.tok.copy_(tok)
@@ -172,11 +173,13 @@ class _SeededSampler:
     ``capture`` records the whole step in ONE HIP graph (one stream, no parallel branches)
     and a token then costs one replay."""
 
-    def __init__(self, model, cache, logits, out, temperature, top_k, top_p, seeds, eos):
+    def __init__(self, model, cache, logits, out, temperature, top_k, top_p, seeds, eos,
+                 adapters=None):
         cfg = model.cfg
         dev = out.device
         B = out.shape[0]
         self.model, self.cache, self.out, self.eos = model, cache, out, eos
+        self.adapters = adapters
         self.buf = torch.empty(B, cfg.padded_vocab, device=dev, dtype=logits.dtype)
         self.logits = self.buf[:, : cfg.vocab_size]
         self.logits.copy_(logits)
@@ -200,7 +203,7 @@ class _SeededSampler:
     def _step(self):
         self.tok = self._draw()
         self.col += 1
-        self.model.decode_step(self.tok, self.cache, out=self.buf)
+        self.model.decode_step(self.tok, self.cache, out=self.buf, adapters=self.adapters)
 
     def draw_last(self):
         """The last token of a call needs no ``decode_step`` after it."""
@@ -238,6 +241,7 @@ class GPT2(nn.Module):
         self.h = nn.ModuleList([Block(cfg) for _ in range(cfg.n_layer)])
         self.ln_f = LayerNorm(cfg.n_embd, cfg.layer_norm_eps)
         self.lm_head_chunk = 8192  # tokens per fused LM-head/CE chunk
+        self.lora = None  # a models.lora.LoRAStack: attach_lora
         self.reset_parameters()
 
     def reset_parameters(self):
@@ -281,12 +285,38 @@ class GPT2(nn.Module):
                                         chunk=self.lm_head_chunk, signal_w=False)
 
     # ------------------------------------------------------------------ generation
+    def attach_lora(self, stack):
+        """Attaches a ``models.lora.LoRAStack`` (``None`` detaches it): the inference passes
+        then take ``adapters``, an int32 [B] tensor on the model's device with one adapter id
+        per row, -1 for the base model, and add each row's adapter after the four linears
+        of every layer (``rf.lora_add``). Without ``adapters`` they run as before. The
+        training ``forward`` never sees the stack."""
+        if stack is not None:
+            cfg, sc = self.cfg, stack.cfg
+            if (sc.n_layer, sc.n_embd) != (cfg.n_layer, cfg.n_embd):
+                raise ValueError("the adapter stack was built for another model size")
+            if stack.device != self.wte.device or stack.dtype != self.wte.dtype:
+                raise ValueError(f"the adapter stack is {stack.dtype} on {stack.device}, the "
+                                 f"model {self.wte.dtype} on {self.wte.device}")
+        self.lora = stack
+
+    def _adapter_ids(self, adapters, B):
+        if adapters is None:
+            return None
+        if self.lora is None:
+            raise ValueError("adapters given, but no adapter stack is attached: attach_lora")
+        if not isinstance(adapters, torch.Tensor) or adapters.dtype != torch.int32 or \
+                adapters.shape != (B,) or adapters.device != self.wte.device:
+            raise ValueError(f"adapters must be an int32 tensor of shape [{B}] on "
+                             f"{self.wte.device}")
+        return adapters
+
     def _flash_ok(self, x) -> bool:
         return x.is_cuda and x.dtype == torch.bfloat16 and \
             self.cfg.n_embd // self.cfg.n_head == 64
 
     @torch.no_grad()
-    def prefill(self, idx, lens, cache: KVCache):
+    def prefill(self, idx, lens, cache: KVCache, adapters=None):
         """Runs the right-padded prompts ``idx`` [B, T] (true lengths ``lens`` [B], >= 1)
         through the model, stores every layer's K/V in ``cache`` and returns the logits of
         each row's last real token, [B, vocab_size]. Causal attention keeps the padding
@@ -302,12 +332,12 @@ class GPT2(nn.Module):
             cache.k[i, :, :, :n].copy_(qkv[:, :n, 1].transpose(1, 2))
             cache.v[i, :, :, :n].copy_(qkv[:, :n, 2].transpose(1, 2))
 
-        logits = self._prefill(idx, lens, store)
+        logits = self._prefill(idx, lens, store, adapters)
         cache.lens = lens.clone()
         return logits
 
     @torch.no_grad()
-    def prefill_into(self, idx, lens, cache: KVCache, slots):
+    def prefill_into(self, idx, lens, cache: KVCache, slots, adapters=None):
         """``prefill`` into rows of a cache that is wider than the prompts' batch: row b of
         ``idx`` [Bn, T] (true lengths ``lens`` [Bn], >= 1) goes to row ``slots[b]`` of
         ``cache`` (``slots`` int32 [Bn] on the device, distinct), through ``rf.kv_insert``:
@@ -321,13 +351,14 @@ class GPT2(nn.Module):
                              f"{idx.device}")
         lens = torch.as_tensor(lens, device=idx.device).to(torch.int32)
         logits = self._prefill(
-            idx, lens, lambda i, qkv: rf.kv_insert(qkv, cache.k[i], cache.v[i], slots, lens))
+            idx, lens, lambda i, qkv: rf.kv_insert(qkv, cache.k[i], cache.v[i], slots, lens),
+            adapters)
         # kv_insert skips a slot id outside the cache
         self._scatter_lens(cache, slots, (slots >= 0) & (slots < cache.lens.shape[0]), lens)
         return logits
 
     @torch.no_grad()
-    def extend_into(self, idx, n_new, cache: KVCache, slots, base):
+    def extend_into(self, idx, n_new, cache: KVCache, slots, base, adapters=None):
         """Continues sequences that already sit in ``cache``: row b of ``idx`` [Bn, Tn]
         (right-padded, true counts ``n_new`` [Bn], >= 1) holds the tokens at positions
         ``base[b] .. base[b] + n_new[b] - 1`` of the sequence in row ``slots[b]``, whose first
@@ -359,7 +390,8 @@ class GPT2(nn.Module):
                                n_new)
             return y.reshape(Bn, Tn, cfg.n_embd)
 
-        logits = self._last_logits(self._layers(self.wte[idx] + self.wpe[pos], attend), n_new)
+        logits = self._last_logits(
+            self._layers(self.wte[idx] + self.wpe[pos], attend, adapters), n_new)
         # the rows that attn_extend skips
         sl, bl, nl = slots.long(), base.long(), n_new.long()
         ok = (sl >= 0) & (sl < cache.lens.shape[0]) & (bl >= 0) & (nl >= 1) & (nl <= Tn) & \
@@ -376,17 +408,33 @@ class GPT2(nn.Module):
         cache.lens.copy_(torch.cat([cache.lens, cache.lens.new_zeros(1)])
                          .scatter_(0, sl, new_lens)[:S])
 
-    def _layers(self, x, attend):
+    def _layers(self, x, attend, adapters=None):
         """The transformer layers of the inference paths on the embedded input ``x``
-        [..., C]; returns ``ln_f`` of the result. ``attend(i, qkv)`` takes layer i's c_attn
-        output [..., 3C] and returns the attention output [..., C], the input of c_proj."""
+        [B, ..., C]; returns ``ln_f`` of the result. ``attend(i, qkv)`` takes layer i's c_attn
+        output [..., 3C] and returns the attention output [..., C], the input of c_proj.
+        ``adapters`` (int32 [B], -1: none): each row's adapter of the attached stack is added
+        to the output of the four linears, before the bias where a later kernel adds it."""
+        adapters = self._adapter_ids(adapters, x.shape[0])
+        if adapters is None:
+            def linear(i, target, inp, w, b=None):
+                return F.linear(inp, w, b)
+        else:
+            st = self.lora
+
+            def linear(i, target, inp, w, b=None):
+                y = F.linear(inp, w, b)
+                rf.lora_add(y, inp, st.a[target][i], st.b[target][i], st.scale, adapters)
+                return y
+
         x, h = self.h[0].ln_1.fork(x)
         for i, blk in enumerate(self.h):
-            a = F.linear(attend(i, F.linear(h, blk.c_attn_w, blk.c_attn_b)), blk.c_proj_w)
+            qkv = linear(i, "c_attn", h, blk.c_attn_w, blk.c_attn_b)
+            a = linear(i, "c_proj", attend(i, qkv), blk.c_proj_w)
             x, h = rf.residual_layer_norm(a, blk.c_proj_b, x, blk.ln_2.weight, blk.ln_2.bias,
                                           blk.ln_2.eps)
             nxt = self.h[i + 1].ln_1 if i + 1 < len(self.h) else self.ln_f
-            m = F.linear(rf.bias_gelu(F.linear(h, blk.c_fc_w), blk.c_fc_b), blk.mlp_proj_w)
+            u = rf.bias_gelu(linear(i, "c_fc", h, blk.c_fc_w), blk.c_fc_b)
+            m = linear(i, "mlp_proj", u, blk.mlp_proj_w)
             x, h = rf.residual_layer_norm(m, blk.mlp_proj_b, x, nxt.weight, nxt.bias, nxt.eps)
         return h
 
@@ -398,7 +446,7 @@ class GPT2(nn.Module):
         hl = h[torch.arange(B, device=h.device), last]
         return F.linear(hl, self.wte)[:, : self.cfg.vocab_size]
 
-    def _prefill(self, idx, lens, store):
+    def _prefill(self, idx, lens, store, adapters=None):
         """The prompt pass of ``prefill`` / ``prefill_into``: ``store(i, qkv)`` takes layer
         i's packed c_attn output [B, Tp, 3, H, hd] (Tp >= T: the padded width)."""
         cfg = self.cfg
@@ -415,11 +463,11 @@ class GPT2(nn.Module):
             store(i, qkv)
             return rf.causal_attention_qkv(qkv).reshape(B, Tp, cfg.n_embd)
 
-        h = self._layers(rf.embedding(idx, self.wte, self.wpe), attend)
+        h = self._layers(rf.embedding(idx, self.wte, self.wpe), attend, adapters)
         return self._last_logits(h, lens)
 
     @torch.no_grad()
-    def decode_step(self, tok, cache: KVCache, out=None):
+    def decode_step(self, tok, cache: KVCache, out=None, adapters=None):
         """One token per row: ``tok`` [B] is the token at position ``cache.lens[b]``;
         appends its K/V to the cache, returns the next-token logits [B, vocab_size] and
         advances ``cache.lens``. No host synchronisation: capturable in a HIP graph, and
@@ -435,7 +483,7 @@ class GPT2(nn.Module):
             y = rf.attn_decode(qkv.view(B, 3, H, hd), cache.k[i], cache.v[i], cache.lens)
             return y.view(B, cfg.n_embd)
 
-        h = self._layers(self.wte[tok] + self.wpe[pos], attend)
+        h = self._layers(self.wte[tok] + self.wpe[pos], attend, adapters)
         if out is None:
             logits = F.linear(h, self.wte)[:, : cfg.vocab_size]
         else:
@@ -455,7 +503,8 @@ class GPT2(nn.Module):
 
     @torch.no_grad()
     def generate(self, idx, max_new_tokens, *, lens=None, temperature=0.0, top_k=None,
-                 top_p=None, seeds=None, eos_token_id=None, generator=None, graph=False):
+                 top_p=None, seeds=None, eos_token_id=None, generator=None, graph=False,
+                 adapters=None):
         """Autoregressive generation with a KV cache: ``idx`` [B, T] prompts, right-padded
         to a common length with true lengths ``lens`` (default: all T). Returns the new
         tokens [B, max_new_tokens] (int64). ``temperature`` 0 is greedy, otherwise samples
@@ -470,9 +519,22 @@ class GPT2(nn.Module):
         token is a hash of the row's seed and the token's position, so a row's tokens
         depend on its prompt, its parameters and its seed only, never on its batch-mates.
         With ``graph=True`` the sampler, the EOS latch and the write into the result are
-        captured with ``decode_step``: a token costs one graph replay and nothing else."""
+        captured with ``decode_step``: a token costs one graph replay and nothing else.
+
+        ``adapters`` (an int, or one per row; -1 or None: the base model) names each row's
+        adapter of the attached ``LoRAStack`` (``attach_lora``); the prompt pass and every
+        step apply it, inside the captured graph too."""
         cfg = self.cfg
         B, T = idx.shape
+        ad = None
+        if adapters is not None:
+            if self.lora is None:
+                raise ValueError("adapters given, but no adapter stack is attached: "
+                                 "attach_lora")
+            ad_l = _per_row("adapters", adapters, -1, B, int)
+            if any(not -1 <= v < self.lora.n_adapters for v in ad_l):
+                raise ValueError(f"adapters must be -1 or in [0, {self.lora.n_adapters})")
+            ad = torch.tensor(ad_l, dtype=torch.int32).to(idx.device)
         if seeds is None:
             if top_p is not None:
                 raise ValueError("top_p needs the device sampler: pass seeds=")
@@ -509,11 +571,12 @@ class GPT2(nn.Module):
             raise ValueError("graph=True needs the model and prompts on the GPU")
         dev = idx.device
         cache = KVCache(cfg, B, max(lens_l) + max_new_tokens, dev, self.wte.dtype)
-        logits = self.prefill(idx, torch.tensor(lens_l, dtype=torch.int32, device=dev), cache)
+        logits = self.prefill(idx, torch.tensor(lens_l, dtype=torch.int32, device=dev), cache,
+                              adapters=ad)
         out = torch.empty(B, max_new_tokens, dtype=torch.long, device=dev)
         if seeds is not None:
             eos = None if eos_token_id is None else int(eos_token_id)
-            step = _SeededSampler(self, cache, logits, out, temps, ks, ps, seeds_l, eos)
+            step = _SeededSampler(self, cache, logits, out, temps, ks, ps, seeds_l, eos, ad)
             if max_new_tokens > 1:
                 step()
                 if graph:
@@ -540,10 +603,10 @@ class GPT2(nn.Module):
                 break
             if not graph or t == 0:
                 # (graph: the first step runs eagerly and warms up what the capture needs)
-                logits = self.decode_step(tok, cache)
+                logits = self.decode_step(tok, cache, adapters=ad)
             else:
                 if step is None:
-                    step = _GraphedStep(self, cache, tok)
+                    step = _GraphedStep(self, cache, tok, ad)
                 logits = step(tok)
         return out
 

@@ -46,6 +46,15 @@ The captured step is untouched. With both options at their defaults the engine d
 did without them. The guarantee above holds with ``prefix + tokens`` as the prompt, for every
 ``prefill_chunk``.
 
+Adapters (``lora=LoRAStack``): ``submit(..., adapter=i)`` names one of the stack's adapters
+for the request. The id goes into ``self.adapter`` (int32 [S], -1: the base model), one more
+fixed-address buffer of the captured step, whose ``decode_step`` applies every slot's own
+adapter (``rf.lora_add``); the prompt passes get the round's ids. ``load_adapter`` /
+``unload_adapter`` rewrite the stack in place between steps, with no re-capture. A prefix
+records the adapter it was prefilled with, since its K/V depend on it. The guarantee above
+holds with ``generate(..., adapters=[adapter])``; without ``lora``, or with no request naming
+an adapter, the engine produces the tokens it produced before.
+
 Single-threaded by contract: every call comes from one thread."""
 
 from __future__ import annotations
@@ -61,18 +70,21 @@ from ray_amd.ops.graph_lock import CapturedStep
 
 
 class _Request:
-    __slots__ = ("rid", "tokens", "max_new", "temperature", "top_k", "top_p", "seed", "pid")
+    __slots__ = ("rid", "tokens", "max_new", "temperature", "top_k", "top_p", "seed", "pid",
+                 "adapter")
 
-    def __init__(self, rid, tokens, max_new, temperature, top_k, top_p, seed, pid=None):
+    def __init__(self, rid, tokens, max_new, temperature, top_k, top_p, seed, pid=None,
+                 adapter=-1):
         # tokens: the whole prompt (the prefix's tokens included); pid: the prefix it names
         self.rid, self.tokens, self.max_new = rid, tokens, max_new
         self.temperature, self.top_k, self.top_p, self.seed = temperature, top_k, top_p, seed
         self.pid = pid
+        self.adapter = adapter  # -1: the base model
 
 
 class GPT2Engine:
     def __init__(self, model: GPT2, slots=8, max_len=None, eos_token_id=None, graph=None,
-                 poll_every=8, prefix_slots=0, prefill_chunk=None):
+                 poll_every=8, prefix_slots=0, prefill_chunk=None, lora=None):
         cfg = model.cfg
         dev = model.wte.device
         S = int(slots)
@@ -108,6 +120,11 @@ class GPT2Engine:
         self.active = torch.zeros(S, dtype=torch.uint8, device=dev)
         self.out = torch.zeros(S, self.max_len, dtype=torch.int64, device=dev)
         self._seen = torch.zeros(S, dtype=torch.int64, device=dev)  # n_out at the last poll
+        self.lora = lora
+        self.adapter = None
+        if lora is not None:
+            model.attach_lora(lora)
+            self.adapter = torch.full((S,), -1, dtype=torch.int32, device=dev)
         self._ar = torch.arange(self.poll_every, device=dev).unsqueeze(0)
 
         self._queue = collections.deque()
@@ -122,7 +139,7 @@ class GPT2Engine:
         if self.prefix_slots:
             self.prefix_cache = KVCache(cfg, self.prefix_slots, self.max_len, dev,
                                         model.wte.dtype)
-        self._prefixes = {}  # pid -> (row of prefix_cache, tokens)
+        self._prefixes = {}  # pid -> (row of prefix_cache, tokens, adapter)
         self._prefix_free = list(range(self.prefix_slots))
         self._next_pid = 0
         self._graph = None
@@ -137,7 +154,7 @@ class GPT2Engine:
                                self.cache.lens, validate=False)
         rf.slot_advance(tok, self.cache.lens, self.n_out, self.max_new, self.active, self.out,
                         self.eos)
-        self.model.decode_step(tok, self.cache, out=self.buf)
+        self.model.decode_step(tok, self.cache, out=self.buf, adapters=self.adapter)
 
     def _run_step(self):
         if self._graph is None:
@@ -160,11 +177,52 @@ class GPT2Engine:
             raise ValueError(f"tokens must be ints in [0, {cfg.vocab_size})")
         return tokens
 
-    def add_prefix(self, tokens):
+    def _checked_adapter(self, adapter):
+        """None -> -1 (the base model); else an int in [0, n_adapters) of the engine's stack."""
+        if adapter is None:
+            return -1
+        if self.lora is None:
+            raise ValueError("adapter given, but the engine has no adapter stack: lora=")
+        if isinstance(adapter, bool) or not isinstance(adapter, int) or \
+                not 0 <= adapter < self.lora.n_adapters:
+            raise ValueError(f"adapter must be an int in [0, {self.lora.n_adapters}), got "
+                             f"{adapter!r}")
+        return adapter
+
+    def _ids(self, adapters):
+        """The round's adapter ids for a prompt pass (None without a stack)."""
+        return None if self.lora is None else adapters.to(torch.int32)
+
+    def _adapter_in_use(self, i):
+        return any(r.adapter == i for r in self._queue) or \
+            any(r is not None and r.adapter == i for r in self._slot_req) or \
+            any(p[2] == i for p in self._prefixes.values())
+
+    def load_adapter(self, i, state, alpha=None):
+        """``lora.load(i, state, alpha)`` between steps, IN PLACE: no re-capture. ``ValueError``
+        while a queued request, a running request or a registered prefix names ``i``."""
+        if self._checked_adapter(i) < 0:
+            raise ValueError("load_adapter needs an adapter slot")
+        if self._adapter_in_use(i):
+            raise ValueError(f"adapter {i} is in use")
+        self.lora.load(i, state, alpha)
+
+    def unload_adapter(self, i):
+        """``lora.clear(i)`` between steps, IN PLACE; ``ValueError`` while ``i`` is in use."""
+        if self._checked_adapter(i) < 0:
+            raise ValueError("unload_adapter needs an adapter slot")
+        if self._adapter_in_use(i):
+            raise ValueError(f"adapter {i} is in use")
+        self.lora.clear(i)
+
+    def add_prefix(self, tokens, adapter=None):
         """Prefills ``tokens`` (1 <= len < max_len) once into a row of the prefix store and
         returns the prefix's id for ``submit(..., prefix=pid)``. ``ValueError`` for bad
-        tokens or a full store (``prefix_slots`` rows), which then holds what it held."""
+        tokens or a full store (``prefix_slots`` rows), which then holds what it held.
+        ``adapter``: the prefix's K/V are those of that adapter, and only requests with the
+        same adapter may name the prefix."""
         tokens = self._checked_tokens(tokens, "prefix")
+        adapter = self._checked_adapter(adapter)
         if len(tokens) >= self.max_len:
             raise ValueError(f"prefix ({len(tokens)}) leaves no room in max_len "
                              f"({self.max_len})")
@@ -175,10 +233,11 @@ class GPT2Engine:
         self.model.prefill_into(torch.tensor([tokens], dtype=torch.long).to(dev),
                                 torch.tensor([len(tokens)], dtype=torch.int32).to(dev),
                                 self.prefix_cache,
-                                torch.tensor([row], dtype=torch.int32).to(dev))
+                                torch.tensor([row], dtype=torch.int32).to(dev),
+                                adapters=self._ids(torch.tensor([adapter]).to(dev)))
         pid = self._next_pid
         self._next_pid += 1
-        self._prefixes[pid] = (row, tokens)
+        self._prefixes[pid] = (row, tokens, adapter)
         return pid
 
     def drop_prefix(self, pid):
@@ -189,15 +248,24 @@ class GPT2Engine:
         self._prefix_free.append(self._prefixes.pop(pid)[0])
 
     def submit(self, tokens, max_new_tokens, temperature=0.0, top_k=None, top_p=None, seed=0,
-               prefix=None):
+               prefix=None, adapter=None):
         """Queues a request and returns its id; a bad request raises ``ValueError`` and
         queues nothing. ``prefix``: an ``add_prefix`` id; ``tokens`` is then the non-empty
-        continuation and the request's prompt is the prefix's tokens followed by it."""
+        continuation and the request's prompt is the prefix's tokens followed by it.
+        ``adapter``: an int in [0, n_adapters) of the engine's stack (None: the base model,
+        or the prefix's adapter when ``prefix`` is given; another adapter than the prefix's
+        is an error)."""
         tokens = self._checked_tokens(tokens, "request")
+        named = adapter is not None
+        adapter = self._checked_adapter(adapter)
         if prefix is not None:
             if not isinstance(prefix, int) or prefix not in self._prefixes:
                 raise ValueError(f"unknown prefix {prefix!r}")
-            tokens =self._prefixes[prefix][1] + tokens
+            if named and adapter != self._prefixes[prefix][2]:
+                raise ValueError(f"prefix {prefix} was prefilled with adapter "
+                                 f"{self._prefixes[prefix][2]}, the request names {adapter}")
+            adapter = self._prefixes[prefix][2]
+            tokens = self._prefixes[prefix][1] + tokens
         max_new = int(max_new_tokens)
         if max_new < 1:
             raise ValueError("max_new_tokens must be >= 1")
@@ -220,7 +288,7 @@ class GPT2Engine:
         rid = self._next_rid
         self._next_rid += 1
         self._queue.append(_Request(rid, tokens, max_new, temperature, top_k, top_p, seed,
-                                    prefix))
+                                    prefix, adapter))
         return rid
 
     def cancel(self, rid):
@@ -268,7 +336,7 @@ class GPT2Engine:
             self._slot_req[s] = r
             self._fill[s] = 0
             if r.pid in self._prefixes:  # (dropped meanwhile: the whole prompt is prefilled)
-                row, head = self._prefixes[r.pid]
+                row, head, _ = self._prefixes[r.pid]
                 copies.append([row, s, len(head)])
                 self._fill[s] = len(head)
         if copies:
@@ -298,7 +366,7 @@ class GPT2Engine:
             idx[b, : lens[b]] = torch.tensor(r.tokens[bases[b]: bases[b] + lens[b]],
                                              dtype=torch.long)
         # three uploads per round and path, however many requests it feeds
-        ints = torch.tensor([[s, n, r.top_k, r.max_new, r.seed, b]
+        ints = torch.tensor([[s, n, r.top_k, r.max_new, r.seed, b, r.adapter]
                              for s, n, r, b in zip(rows, lens, reqs, bases)],
                             dtype=torch.int64).to(dev)
         flts = torch.tensor([[r.temperature, r.top_p] for r in reqs],
@@ -306,10 +374,12 @@ class GPT2Engine:
         sl = ints[:, 0]
         if ext:
             logits = self.model.extend_into(idx.to(dev), ints[:, 1].to(torch.int32), self.cache,
-                                            sl.to(torch.int32), ints[:, 5].to(torch.int32))
+                                            sl.to(torch.int32), ints[:, 5].to(torch.int32),
+                                            adapters=self._ids(ints[:, 6]))
         else:
             logits = self.model.prefill_into(idx.to(dev), ints[:, 1].to(torch.int32),
-                                             self.cache, sl.to(torch.int32))
+                                             self.cache, sl.to(torch.int32),
+                                             adapters=self._ids(ints[:, 6]))
         done = [j for j, r in enumerate(reqs) if bases[j] + lens[j] == len(r.tokens)]
         for j, s in enumerate(rows):
             self._fill[s] = bases[j] + lens[j]
@@ -326,6 +396,8 @@ class GPT2Engine:
         self.top_k.index_copy_(0, sl, ints[:, 2].to(torch.int32))
         self.max_new.index_copy_(0, sl, ints[:, 3].to(torch.int32))
         self.seeds.index_copy_(0, sl, ints[:, 4])
+        if self.adapter is not None:
+            self.adapter.index_copy_(0, sl, ints[:, 6].to(torch.int32))
         self.temperature.index_copy_(0, sl, flts[:, 0])
         self.top_p.index_copy_(0, sl, flts[:, 1])
         self.n_out.index_fill_(0, sl, 0)

@@ -127,6 +127,7 @@ _SIGS = {
     "ra_kv_insert": [c_void_p] * 5 + [c_int] * 5 + [c_void_p],
     "ra_kv_copy": [c_void_p] * 7 + [c_int] * 7 + [c_void_p],
     "ra_attn_extend": [c_void_p] * 7 + [c_int] * 5 + [c_float, c_void_p],
+    "ra_lora_add": [c_void_p] * 6 + [c_int] * 6 + [c_void_p],
     "ra_slot_advance": [c_void_p] * 6 + [c_int, c_int, c_long, c_void_p],
     "ra_sample_logits_max_v": [],
     "ra_sample_logits": [c_void_p, c_long] + [c_void_p] * 6 + [c_int, c_void_p, c_int, c_int,

@@ -784,6 +784,73 @@ def kv_copy(src_k, src_v, dst_k, dst_v, src_rows, dst_rows, lens):
                                 stream_ptr()), "kv_copy")
 
 
+LORA_RANKS = (16, 32, 48, 64)  # what ops/csrc/lora.hip takes; loaders zero-pad up to these
+
+
+def lora_add(y, x, a_stack, b_stack, scale, idx):
+    """Per-row low-rank adapters, ``y`` written IN PLACE; returns None::
+
+        x        [Bn, T, Din]  (or [Bn, Din], T = 1)   bf16, contiguous
+        y        [Bn, T, Dout] (same leading shape)    bf16, contiguous
+        a_stack  [n_adapters, R, Din]                  bf16
+        b_stack  [n_adapters, Dout, R]                 bf16
+        scale    [n_adapters]                          fp32, on the device
+        idx      [Bn]                                  int32, on the device
+
+    For every row b with ``0 <= idx[b] < n_adapters`` and every token i, with ``a = idx[b]``:
+    ``t = bf16(fp32 sum_k x[b,i,k] * a_stack[a,:,k])`` (R values, rounded once), then
+    ``y[b,i,:] = bf16(float(y[b,i,:]) + scale[a] * fp32 sum_r t[r] * b_stack[a,:,r])``.
+    Rows with ``idx[b]`` outside that range are not touched: their bytes stay as they are,
+    NaN payloads included, which is how a base-model request rides in a batch with adapted
+    ones (``idx = -1``). ``idx`` and ``scale`` are only read, on the device: no host sync, one
+    launch on the current stream, no atomics; capturable, and one capture serves every
+    assignment of adapters to rows. A token's output bits depend only on its own ``x`` row,
+    its own ``y`` row and its adapter's ``A``, ``B`` and ``scale``, never on Bn, T, the row's
+    index or the other rows. Semantics: ``reference.lora_add``.
+
+    HIP MFMA kernel (ops/csrc/lora.hip) for bf16 GPU tensors with R in {16, 32, 48, 64} and
+    Din, Dout multiples of 64; CPU tensors, other dtypes and other sizes use the plain-torch
+    reference. Inference only. Bad arguments raise ``ValueError`` before anything runs."""
+    op = "lora_add"
+    ts = (("y", y), ("x", x), ("a_stack", a_stack), ("b_stack", b_stack), ("scale", scale),
+          ("idx", idx))
+    for name, t in ts:
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{op}: {name} must be a tensor")
+        if t.requires_grad:
+            raise ValueError(f"{op} is an inference op: {name} must not require grad")
+        if t.device != y.device:
+            raise ValueError(f"{op}: {name} is on {t.device}, y on {y.device}")
+    if x.dim() not in (2, 3) or y.dim() != x.dim() or x.shape[:-1] != y.shape[:-1]:
+        raise ValueError(f"{op}: x must be [Bn, T, Din] or [Bn, Din] and y the same with Dout, "
+                         f"got {tuple(x.shape)} and {tuple(y.shape)}")
+    Bn, Din, Dout = x.shape[0], x.shape[-1], y.shape[-1]
+    T = x.shape[1] if x.dim() == 3 else 1
+    if a_stack.dim() != 3 or b_stack.dim() != 3:
+        raise ValueError(f"{op}: a_stack must be [n_adapters, R, Din], b_stack "
+                         f"[n_adapters, Dout, R]")
+    NA, R = a_stack.shape[0], a_stack.shape[1]
+    if a_stack.shape != (NA, R, Din) or b_stack.shape != (NA, Dout, R):
+        raise ValueError(f"{op}: a_stack {tuple(a_stack.shape)} and b_stack "
+                         f"{tuple(b_stack.shape)} do not fit Din {Din}, Dout {Dout}")
+    if min(Bn, T, Din, Dout, NA, R) < 1:
+        raise ValueError(f"{op}: empty argument")
+    if len({y.dtype, x.dtype, a_stack.dtype, b_stack.dtype}) != 1 or not y.is_floating_point():
+        raise ValueError(f"{op}: y, x and the stacks must share one floating dtype")
+    if scale.shape != (NA,) or scale.dtype != torch.float32:
+        raise ValueError(f"{op}: scale must be a float32 tensor of shape [{NA}]")
+    _int_vec("idx", op, idx, Bn, y)
+    if not y.is_contiguous():
+        raise ValueError(f"{op}: y is written in place and must be contiguous")
+    if not (_hip(y) and y.dtype == torch.bfloat16 and R in LORA_RANKS and Din % 64 == 0
+            and Dout % 64 == 0):
+        return ref.lora_add(y, x, a_stack, b_stack, scale, idx)
+    x, a_stack, b_stack = x.contiguous(), a_stack.contiguous(), b_stack.contiguous()
+    check(_lib.lib().ra_lora_add(ptr(y), ptr(x), ptr(a_stack), ptr(b_stack),
+                                 ptr(scale.contiguous()), ptr(idx.contiguous()), Bn, T, Din, Dout,
+                                 R, NA, stream_ptr()), op)
+
+
 def slot_advance(tok, lens, n_out, max_new, active, out, eos_token_id=None):
     """The continuous-batching engine's bookkeeping after the sampler, one launch, IN
     PLACE: an active slot with ``n_out[s] < cap`` stores ``out[s, n_out[s]] = tok[s]``,

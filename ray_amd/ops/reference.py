@@ -202,6 +202,47 @@ def slot_advance(tok, lens, n_out, max_new, active, out, eos_token_id=None):
     lens.masked_fill_(~stay, SLOT_INACTIVE)
 
 
+def _lora_rows(y, x, a_stack, b_stack, idx):
+    """The views and the per-row adapter choice both LoRA forms share: ``(y3, x3, A, B, ic,
+    ok)`` with A, B the rows' adapters (a clamped id for the rows that have none)."""
+    Bn, NA = idx.shape[0], a_stack.shape[0]
+    i = idx.long()
+    ok = ((i >= 0) & (i < NA)).view(Bn, 1, 1)
+    ic = i.clamp(0, NA - 1)
+    return (y.view(Bn, -1, y.shape[-1]), x.reshape(Bn, -1, x.shape[-1]),
+            a_stack.index_select(0, ic), b_stack.index_select(0, ic), ic, ok)
+
+
+def lora_add(y, x, a_stack, b_stack, scale, idx):
+    """Per-row low-rank adapters (ops/csrc/lora.hip semantics): the single definition of
+    them. ``x`` [Bn, T, Din] or [Bn, Din], ``y`` [Bn, T, Dout] or [Bn, Dout] written IN
+    PLACE, ``a_stack`` [n_adapters, R, Din], ``b_stack`` [n_adapters, Dout, R], ``scale``
+    [n_adapters], ``idx`` integer [Bn].
+
+    For every row b with 0 <= idx[b] < n_adapters, a = idx[b], and every token i:
+    ``t = sum_k x[b,i,k] * a_stack[a,:,k]`` in fp32, rounded ONCE to the input dtype (not at
+    all for fp32 inputs), then ``y[b,i,:] = (float(y[b,i,:]) + scale[a] * sum_r t[r] *
+    b_stack[a,:,r])`` rounded to y's dtype. Every other row keeps its bytes. No host sync."""
+    ct = torch.float64 if x.dtype == torch.float64 else torch.float32
+    y3, x3, A, B, ic, ok = _lora_rows(y, x, a_stack, b_stack, idx)
+    t = x3.to(ct) @ A.to(ct).transpose(1, 2)
+    t = t.to(x.dtype).to(ct)
+    d = t @ B.to(ct).transpose(1, 2)
+    new = (y3.to(ct) + scale.to(ct)[ic].view(-1, 1, 1) * d).to(y.dtype)
+    y3.copy_(torch.where(ok, new, y3))
+
+
+def lora_add_bmm(y, x, a_stack, b_stack, scale, idx):
+    """``lora_add`` as the usual torch composition: ``index_select`` of the stacks by the
+    clamped ids, two ``bmm`` in the tensors' own dtype, rows without an adapter masked out.
+    Same contract and no host sync, but the sums' order is the GEMM library's. The baseline
+    ``scripts/lora_bench.py`` measures the HIP kernel against."""
+    y3, x3, A, B, ic, ok = _lora_rows(y, x, a_stack, b_stack, idx)
+    d = torch.bmm(torch.bmm(x3, A.transpose(1, 2)), B.transpose(1, 2))
+    new = (y3.float() + scale[ic].view(-1, 1, 1) * d.float()).to(y.dtype)
+    y3.copy_(torch.where(ok, new, y3))
+
+
 _MASK64 = (1 << 64) - 1
 
 

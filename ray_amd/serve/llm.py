@@ -29,7 +29,12 @@ tokens as they are produced. The same request fields and the same per-request gu
 ``prefixes={"name": [tokens], ...}`` registers shared prompt prefixes with the engine at
 start-up (each is prefilled once); a request may then carry ``"prefix": "name"`` and its
 ``tokens`` are the continuation: it answers what the request with the whole prompt answers.
-``prefill_chunk=C`` bounds the prompt tokens a request is fed per engine step."""
+``prefill_chunk=C`` bounds the prompt tokens a request is fed per engine step.
+``adapters={"name": path_or_state_dict, ...}`` loads low-rank adapters (``models/lora.py``,
+up to ``lora_rank``) into the engine at start-up; a request may then carry ``"adapter":
+"name"`` and shares its decode steps with requests of other adapters and of the base model.
+A prefix may be bound to an adapter: ``prefixes={"name": {"tokens": [...], "adapter":
+"name"}}``."""
 
 from __future__ import annotations
 
@@ -89,6 +94,9 @@ class GPT2Server:
         if r.get("prefix") is not None:
             raise ValueError("'prefix' needs the continuous engine: build_gpt2_app("
                              "continuous=True, prefixes=...)")
+        if r.get("adapter") is not None:
+            raise ValueError("'adapter' needs the continuous engine: build_gpt2_app("
+                             "continuous=True, adapters=...)")
         return _request_params(self.model.cfg, self.seed, r)
 
     def _run_sampled(self, reqs, params):
@@ -200,7 +208,7 @@ class GPT2EngineServer:
 
     def __init__(self, config="small", state_dict_path=None, seed=0, slots=None,
                  eos_token_id=None, device=None, poll_every=None, prefixes=None,
-                 prefill_chunk=None):
+                 prefill_chunk=None, adapters=None, lora_rank=16):
         import queue
         import threading
 
@@ -211,7 +219,12 @@ class GPT2EngineServer:
         self._inbox = queue.Queue()
         self._next_key = 0
         self._failure = None
-        self._prefixes = {k: list(v) for k, v in (prefixes or {}).items()}
+        # prefix name -> (tokens, adapter name or None)
+        self._prefixes = {k: (list(v["tokens"]), v.get("adapter")) if isinstance(v, dict)
+                          else (list(v), None) for k, v in (prefixes or {}).items()}
+        self._adapters = dict(adapters or {})  # adapter name -> path or state dict
+        self._lora_rank = int(lora_rank)
+        self._aids = {}  # adapter name -> the engine's adapter slot
         self._prefill_chunk = prefill_chunk
         self._pids = {}  # prefix name -> the engine's prefix id
         ready = threading.Event()
@@ -239,11 +252,23 @@ class GPT2EngineServer:
                 torch.cuda.set_device(self.device)
                 model = model.to(self.device, torch.bfloat16)
             kw = {} if poll_every is None else {"poll_every": int(poll_every)}
+            if self._adapters:
+                from ray_amd.models.lora import LoRAStack
+
+                kw["lora"] = LoRAStack(self.cfg, len(self._adapters), self._lora_rank,
+                                       model.wte.device, model.wte.dtype)
             eng = GPT2Engine(model.eval(), slots=slots, eos_token_id=eos_token_id,
                              prefix_slots=len(self._prefixes),
                              prefill_chunk=self._prefill_chunk, **kw)
-            for name, toks in self._prefixes.items():
-                self._pids[name] = eng.add_prefix(toks)
+            for i, (name, state) in enumerate(self._adapters.items()):
+                if not isinstance(state, dict):
+                    state = torch.load(state, map_location="cpu")
+                eng.load_adapter(i, state)
+                self._aids[name] = i
+            for name, (toks, adapter) in self._prefixes.items():
+                if adapter is not None and adapter not in self._aids:
+                    raise ValueError(f"prefix {name!r} names the unknown adapter {adapter!r}")
+                self._pids[name] = eng.add_prefix(toks, adapter=self._aids.get(adapter))
             self.engine = eng
         except BaseException as e:  # noqa: BLE001  (reported to the constructor's caller)
             self._failure = e
@@ -274,7 +299,8 @@ class GPT2EngineServer:
                 try:
                     rid = eng.submit(req["tokens"], p[1], temperature=p[2], top_k=p[3],
                                      top_p=p[4], seed=p[5],
-                                     prefix=self._pids.get(req.get("prefix")))
+                                     prefix=self._pids.get(req.get("prefix")),
+                                     adapter=self._aids.get(req.get("adapter")))
                 except ValueError as e:
                     loop.call_soon_threadsafe(sink.put_nowait, ("error", f"ValueError: {e}"))
                     continue
@@ -314,6 +340,9 @@ class GPT2EngineServer:
             name = request.get("prefix")
             if name is not None and (not isinstance(name, str) or name not in self._pids):
                 raise ValueError(f"unknown prefix {name!r}")
+            name = request.get("adapter")
+            if name is not None and (not isinstance(name, str) or name not in self._aids):
+                raise ValueError(f"unknown adapter {name!r}")
         except Exception as e:  # noqa: BLE001  (a bad request touches nothing else)
             yield ("error", f"{type(e).__name__}: {e}")
             return
@@ -358,7 +387,8 @@ class GPT2EngineServer:
 
 def build_gpt2_app(config="small", state_dict_path=None, seed=0, max_batch_size=8,
                    batch_wait_timeout_s=0.01, device=None, continuous=False, slots=None,
-                   eos_token_id=None, prefixes=None, prefill_chunk=None):
+                   eos_token_id=None, prefixes=None, prefill_chunk=None, adapters=None,
+                   lora_rank=16):
     """A Serve application around one ``GPT2Server`` replica (``serve.run`` it). ``config``
     names a ``GPT2Config`` preset; without ``state_dict_path`` the weights are the seeded
     random init. ``device`` None: the GPU assigned to the replica, else the CPU.
@@ -367,12 +397,16 @@ def build_gpt2_app(config="small", state_dict_path=None, seed=0, max_batch_size=
     ``slots`` (default 8) KV-cache slots with streaming, requests ending at
     ``eos_token_id``; ``max_batch_size`` and ``batch_wait_timeout_s`` do not apply.
     ``prefixes`` (``{"name": [tokens], ...}``: shared prompt prefixes a request names with
-    ``"prefix": "name"``) and ``prefill_chunk`` need ``continuous=True``."""
+    ``"prefix": "name"``) and ``prefill_chunk`` need ``continuous=True``. So does ``adapters``
+    (``{"name": path_or_state_dict, ...}``: low-rank adapters of rank up to ``lora_rank`` in
+    the ``LoRAStack.load`` format, paths read with ``torch.load``), which a request names
+    with ``"adapter": "name"``; a ``prefixes`` value may be ``{"tokens": [...], "adapter":
+    "name"}``."""
     if continuous:
         dep = deployment(GPT2EngineServer, name="GPT2EngineServer")
         return dep.bind(config, state_dict_path, seed, slots, eos_token_id, device, None,
-                        prefixes, prefill_chunk)
-    if prefixes or prefill_chunk is not None:
-        raise ValueError("prefixes and prefill_chunk need continuous=True")
+                        prefixes, prefill_chunk, adapters, lora_rank)
+    if prefixes or prefill_chunk is not None or adapters:
+        raise ValueError("prefixes, prefill_chunk and adapters need continuous=True")
     dep = deployment(GPT2Server, name="GPT2Server")
     return dep.bind(config, state_dict_path, seed, max_batch_size, batch_wait_timeout_s, device)
