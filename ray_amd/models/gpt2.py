@@ -32,6 +32,8 @@ MI355X-first choices:
   the admission path of the continuous-batching engine, models/gpt2_engine.py.
   ``extend_into`` continues rows of such a cache with several new tokens each
   (ops/csrc/attn_extend.hip): the engine's shared prompt prefixes and chunked prefill.
+  ``verify_step`` runs the same layers over a window of drafted tokens per row and returns
+  the logits after every one of them: the engine's speculative decoding.
   The three inference passes (prompt, extend, decode) run ONE layer loop, ``_layers``, and
   hand it their attention step; the training ``forward`` keeps its own (autograd ops).
 """
@@ -145,6 +147,7 @@ class KVCache:
         self.k = torch.zeros(shape, device=device, dtype=dtype)
         self.v = torch.zeros(shape, device=device, dtype=dtype)
         self.lens = torch.zeros(batch, device=device, dtype=torch.int32)
+        self.rows = torch.arange(batch, device=device, dtype=torch.int32)  # verify_step's slots
         self.max_len = max_len
 
 
@@ -370,7 +373,6 @@ class GPT2(nn.Module):
         ``lens`` of every slot that is not decoding). Writes ``cache.lens[slots] = base +
         n_new`` IN PLACE for the rows ``rf.attn_extend`` treats as active and returns the
         logits of each row's last real token, [Bn, vocab_size]. No host synchronisation."""
-        cfg = self.cfg
         Bn, Tn = idx.shape
         for name, t in (("slots", slots), ("base", base)):
             if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or \
@@ -380,6 +382,21 @@ class GPT2(nn.Module):
         if Bn < 1 or Tn < 1:
             raise ValueError("extend_into needs at least one token in every row")
         n_new = torch.as_tensor(n_new, device=idx.device).to(torch.int32)
+        logits = self._last_logits(self._extend(idx, n_new, cache, slots, base, adapters),
+                                   n_new)
+        # the rows that attn_extend skips
+        sl, bl, nl = slots.long(), base.long(), n_new.long()
+        ok = (sl >= 0) & (sl < cache.lens.shape[0]) & (bl >= 0) & (nl >= 1) & (nl <= Tn) & \
+            (bl + nl <= cache.k.shape[3])
+        self._scatter_lens(cache, sl, ok, (bl + nl).to(torch.int32))
+        return logits
+
+    def _extend(self, idx, n_new, cache, slots, base, adapters=None):
+        """The layers of ``extend_into`` / ``verify_step``: the tokens ``idx`` [Bn, Tn] at
+        positions ``base[b] + i`` through ``rf.attn_extend`` over rows ``slots`` of ``cache``;
+        returns ``ln_f`` of the result, [Bn, Tn, C]. Leaves ``cache.lens`` alone."""
+        cfg = self.cfg
+        Bn, Tn = idx.shape
         H, hd = cfg.n_head, cfg.n_embd // cfg.n_head
         # the padding's positions are clamped into the table; its outputs are dropped
         pos = (base.long().view(Bn, 1) + torch.arange(Tn, device=idx.device)).clamp(
@@ -390,14 +407,38 @@ class GPT2(nn.Module):
                                n_new)
             return y.reshape(Bn, Tn, cfg.n_embd)
 
-        logits = self._last_logits(
-            self._layers(self.wte[idx] + self.wpe[pos], attend, adapters), n_new)
-        # the rows that attn_extend skips
-        sl, bl, nl = slots.long(), base.long(), n_new.long()
-        ok = (sl >= 0) & (sl < cache.lens.shape[0]) & (bl >= 0) & (nl >= 1) & (nl <= Tn) & \
-            (bl + nl <= cache.k.shape[3])
-        self._scatter_lens(cache, sl, ok, (bl + nl).to(torch.int32))
-        return logits
+        return self._layers(self.wte[idx] + self.wpe[pos], attend, adapters)
+
+    @torch.no_grad()
+    def verify_step(self, win, n_win, cache: KVCache, out=None, adapters=None):
+        """The verify pass of a speculative decode step: row s of ``win`` [S, W] (int64) holds
+        ``n_win[s]`` tokens (int32 [S] on the device; the rest is padding) at positions
+        ``cache.lens[s] + i`` of the sequence in row s of ``cache`` (S rows). Every layer
+        goes through ``rf.attn_extend`` with ``slots = arange(S)``, ``base = cache.lens`` and
+        ``n_new = n_win``: the window's K/V are appended to the row and token i attends over
+        the cached positions and the window up to itself. ALL W positions meet the tied LM
+        head: returns [S, W, vocab_size], where ``[s, i]`` are the logits after ``win[s, i]``
+        (a view of ``out`` [S, W, padded_vocab] when given). ``cache.lens`` is NOT written:
+        whoever decides how much of the window stands advances it (``rf.spec_accept``). A row
+        with ``n_win[s] = 0`` or an inactive ``cache.lens[s]`` writes nothing to the cache,
+        and its logits mean nothing. No host read: capturable."""
+        cfg = self.cfg
+        S = cache.lens.shape[0]
+        if win.dim() != 2 or win.shape[0] != S or win.shape[1] < 1 or win.dtype != torch.int64:
+            raise ValueError(f"win must be an int64 tensor [{S}, W], the cache's rows")
+        W = win.shape[1]
+        if not isinstance(n_win, torch.Tensor) or n_win.dtype != torch.int32 or \
+                n_win.shape != (S,) or n_win.device != win.device:
+            raise ValueError(f"n_win must be an int32 tensor of shape [{S}] on {win.device}")
+        # (a drafter's token is clamped into the table: memory safety is not its contract)
+        h = self._extend(win.clamp(0, cfg.vocab_size - 1), n_win, cache, cache.rows, cache.lens,
+                         adapters)
+        if out is None:
+            return F.linear(h, self.wte)[..., : cfg.vocab_size]
+        if out.shape != (S, W, cfg.padded_vocab) or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous [{S}, {W}, {cfg.padded_vocab}] tensor")
+        torch.mm(h.reshape(S * W, cfg.n_embd), self.wte.t(), out=out.view(S * W, -1))
+        return out[..., : cfg.vocab_size]
 
     @staticmethod
     def _scatter_lens(cache, slots, ok, new_lens):

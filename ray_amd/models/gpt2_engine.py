@@ -55,6 +55,29 @@ records the adapter it was prefilled with, since its K/V depend on it. The guara
 holds with ``generate(..., adapters=[adapter])``; without ``lora``, or with no request naming
 an adapter, the engine produces the tokens it produced before.
 
+Speculative decoding (``speculate=k``, 1..8; 0, the default, is the engine without it):
+a device step then emits between 1 and k + 1 tokens per slot. After the sampler has drawn
+``tok0`` for position ``lens[s]``, a drafter proposes up to k tokens to follow it, ONE
+``GPT2.verify_step`` runs the whole window through the model (``rf.attn_extend`` over the
+slot's cache, the logits after every window token), the sampler draws a token from each
+of them with the hash step of ITS position, and ``rf.spec_accept`` keeps the drafts up to
+the first one the sampler disagrees with. The sampler's randomness is a hash of (seed,
+position), so the token at a position is a function of the logits there and the request's
+parameters: an accepted draft IS the token the plain step would have drawn. There is no
+rejection sampling and the output distribution does not change, for greedy and sampled
+requests alike; the guarantee above holds for every k and every drafter that keeps its
+contract. The default drafter is prompt lookup, ``rf.spec_draft``: the tokens that followed
+the most recent earlier occurrence of the request's last ``ngram[1]`` .. ``ngram[0]``
+tokens, looked up on the device in ``hist``, the request's tokens by position. Drafting
+and accepting are two small integer kernels (ops/csrc/spec.hip), so the speculative step
+touches nothing on the host either and is one graph replay. ``drafter``: any capturable
+device function ``(tok0, hist, lens, n_out, max_new, active) -> (win int64 [S, k + 1],
+n_win int32 [S])`` with ``win[:, 0] == tok0`` and ``0 <= n_win - 1 <= min(k, room - 1)``,
+``room = min(max_new - n_out, max_len - lens)``, for the active slots and ``n_win = 0``
+for the others: the hook for a draft model. Memory safety does not depend on that
+contract (every kernel checks its bounds), the tokens do. ``spec_stats()`` reports how
+many drafts were proposed and how many accepted.
+
 Single-threaded by contract: every call comes from one thread."""
 
 from __future__ import annotations
@@ -84,7 +107,8 @@ class _Request:
 
 class GPT2Engine:
     def __init__(self, model: GPT2, slots=8, max_len=None, eos_token_id=None, graph=None,
-                 poll_every=8, prefix_slots=0, prefill_chunk=None, lora=None):
+                 poll_every=8, prefix_slots=0, prefill_chunk=None, lora=None, speculate=0,
+                 ngram=(2, 4), drafter=None):
         cfg = model.cfg
         dev = model.wte.device
         S = int(slots)
@@ -96,6 +120,18 @@ class GPT2Engine:
             raise ValueError("prefix_slots must be >= 0")
         if prefill_chunk is not None and int(prefill_chunk) < 1:
             raise ValueError("prefill_chunk must be None or >= 1")
+        if isinstance(speculate, bool) or not isinstance(speculate, int) or \
+                not 0 <= speculate <= rf.SPEC_MAX_DRAFTS:
+            raise ValueError(f"speculate must be an int in 0..{rf.SPEC_MAX_DRAFTS}, got "
+                             f"{speculate!r}")
+        try:
+            lo, hi = (int(n) for n in ngram)
+        except (TypeError, ValueError):
+            raise ValueError(f"ngram must be a pair (min, max), got {ngram!r}") from None
+        if not 1 <= lo <= hi <= rf.SPEC_MAX_NGRAM:
+            raise ValueError(f"ngram needs 1 <= min <= max <= {rf.SPEC_MAX_NGRAM}, got {ngram!r}")
+        if drafter is not None and not speculate:
+            raise ValueError("a drafter needs speculate >= 1")
         if graph is None:
             graph = dev.type == "cuda"
         if graph and dev.type != "cuda":
@@ -125,7 +161,26 @@ class GPT2Engine:
         if lora is not None:
             model.attach_lora(lora)
             self.adapter = torch.full((S,), -1, dtype=torch.int32, device=dev)
-        self._ar = torch.arange(self.poll_every, device=dev).unsqueeze(0)
+        self.speculate, self.ngram = speculate, (lo, hi)
+        self._drafter = drafter
+        if speculate:
+            W = speculate + 1  # the window: the sampled token and the drafts
+            self.hist = torch.zeros(S, self.max_len, dtype=torch.int32, device=dev)
+            self.win = torch.zeros(S, W, dtype=torch.int64, device=dev)
+            self.n_win = torch.zeros(S, dtype=torch.int32, device=dev)
+            self.logits_win = torch.zeros(S, W, cfg.padded_vocab, device=dev,
+                                          dtype=model.wte.dtype)
+            self.n_drafted = torch.zeros(S, dtype=torch.int32, device=dev)
+            self.n_accepted = torch.zeros(S, dtype=torch.int32, device=dev)
+            # every slot's sampler parameters once per window row (written at admission),
+            # and the window rows' distance from lens
+            self._win_params = [torch.zeros(S, W, dtype=t.dtype, device=dev)
+                                for t in (self.temperature, self.top_k, self.top_p, self.seeds)]
+            self._win_offs = torch.arange(1, W + 1, dtype=torch.int32, device=dev).unsqueeze(0)
+            if drafter is None:
+                self._drafter = self._ngram_drafter
+        # a poll carries what poll_every steps can emit per slot
+        self._ar = torch.arange(self.poll_every * (speculate + 1), device=dev).unsqueeze(0)
 
         self._queue = collections.deque()
         self._slot_req = [None] * S  # the request running in each slot
@@ -150,11 +205,43 @@ class GPT2Engine:
 
     # ------------------------------------------------------------------ the device step
     def _device_step(self):
+        if self.speculate:
+            return self._spec_step()
         tok = rf.sample_logits(self.logits, self.temperature, self.top_k, self.top_p, self.seeds,
                                self.cache.lens, validate=False)
         rf.slot_advance(tok, self.cache.lens, self.n_out, self.max_new, self.active, self.out,
                         self.eos)
         self.model.decode_step(tok, self.cache, out=self.buf, adapters=self.adapter)
+
+    def _ngram_drafter(self, tok0, hist, lens, n_out, max_new, active):
+        return rf.spec_draft(tok0, hist, lens, n_out, max_new, active, self.speculate,
+                             *self.ngram, win=self.win, n_win=self.n_win)
+
+    def _spec_step(self):
+        """The speculative step, five calls: sample, draft, verify, sample the window, accept."""
+        S, W, V = self.slots, self.speculate + 1, self.model.cfg.vocab_size
+        lens = self.cache.lens
+        tok0 = rf.sample_logits(self.logits, self.temperature, self.top_k, self.top_p, self.seeds,
+                                lens, validate=False)
+        win, n_win = self._drafter(tok0, self.hist, lens, self.n_out, self.max_new, self.active)
+        self.model.verify_step(win, n_win, self.cache, out=self.logits_win,
+                               adapters=self.adapter)
+        temperature, top_k, top_p, seeds = (t.view(S * W) for t in self._win_params)
+        # window row i holds the logits at position lens + 1 + i
+        cand = rf.sample_logits(self.logits_win.view(S * W, -1)[:, :V], temperature, top_k, top_p,
+                                seeds, (lens.unsqueeze(1) + self._win_offs).view(S * W),
+                                validate=False)
+        rf.spec_accept(win, n_win, cand.view(S, W), self.logits_win, lens, self.n_out,
+                       self.max_new, self.active, self.out, self.hist, self.buf, self.n_drafted,
+                       self.n_accepted, self.eos)
+
+    def spec_stats(self):
+        """``{"drafted": n, "accepted": m}``: the draft tokens the verify passes checked so
+        far and the ones that became output, over all requests. One download."""
+        if not self.speculate:
+            return {"drafted": 0, "accepted": 0}
+        n, m = torch.stack([self.n_drafted.sum(), self.n_accepted.sum()]).tolist()
+        return {"drafted": n, "accepted": m}
 
     def _run_step(self):
         if self._graph is None:
@@ -402,6 +489,16 @@ class GPT2Engine:
         self.top_p.index_copy_(0, sl, flts[:, 1])
         self.n_out.index_fill_(0, sl, 0)
         self._seen.index_fill_(0, sl, 0)
+        if self.speculate:
+            # the whole prompt by position, for the drafter: one more upload per round
+            rows_h = torch.zeros(len(done), self.max_len, dtype=torch.int32)
+            for i, j in enumerate(done):
+                rows_h[i, : len(reqs[j].tokens)] = torch.tensor(reqs[j].tokens,
+                                                               dtype=torch.int32)
+            self.hist.index_copy_(0, sl, rows_h.to(dev))
+            for wide, one in zip(self._win_params,
+                                 (self.temperature, self.top_k, self.top_p, self.seeds)):
+                wide.copy_(one.unsqueeze(1).expand_as(wide))
         self.active.index_fill_(0, sl, 1)
         for j in done:
             self._fill[rows[j]] = None
@@ -409,8 +506,8 @@ class GPT2Engine:
 
     # ------------------------------------------------------------------ poll
     def _poll(self):
-        """One download, whatever S: per slot n_out, active and the (at most poll_every)
-        tokens it produced since the last poll."""
+        """One download, whatever S: per slot n_out, active and the (at most poll_every, times
+        speculate + 1) tokens it produced since the last poll."""
         col = (self._seen.unsqueeze(1) + self._ar).clamp_(max=self.max_len - 1)
         host = torch.cat([self.n_out.long().unsqueeze(1), self.active.long().unsqueeze(1),
                           self.out.gather(1, col)], 1).tolist()

@@ -129,6 +129,8 @@ _SIGS = {
     "ra_attn_extend": [c_void_p] * 7 + [c_int] * 5 + [c_float, c_void_p],
     "ra_lora_add": [c_void_p] * 6 + [c_int] * 6 + [c_void_p],
     "ra_slot_advance": [c_void_p] * 6 + [c_int, c_int, c_long, c_void_p],
+    "ra_spec_draft": [c_void_p] * 8 + [c_int] * 5 + [c_void_p],
+    "ra_spec_accept": [c_void_p] * 13 + [c_int] * 4 + [c_long, c_void_p],
     "ra_sample_logits_max_v": [],
     "ra_sample_logits": [c_void_p, c_long] + [c_void_p] * 6 + [c_int, c_void_p, c_int, c_int,
                                                                 c_void_p],

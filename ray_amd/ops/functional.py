@@ -881,6 +881,136 @@ def slot_advance(tok, lens, n_out, max_new, active, out, eos_token_id=None):
                                      out.shape[1], eos, stream_ptr()), "slot_advance")
 
 
+SPEC_MAX_DRAFTS = 8  # ops/csrc/spec.hip kSpecMaxK
+SPEC_MAX_NGRAM = 8   # ops/csrc/spec.hip kSpecMaxN
+
+
+def _spec_table(name, op, t, S, like, dtype, cols=None):
+    """``t`` is a ``dtype`` tensor [S, cols] (any cols >= 1 when None) on ``like``'s device."""
+    if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[0] != S or t.shape[1] < 1 or \
+            (cols is not None and t.shape[1] != cols) or t.dtype != dtype or \
+            t.device != like.device:
+        raise ValueError(f"{op}: {name} must be a {dtype} tensor [{S}, "
+                         f"{'cols' if cols is None else cols}] on {like.device}")
+
+
+def spec_draft(tok0, hist, lens, n_out, max_new, active, k, ngram_min=2, ngram_max=4, win=None,
+               n_win=None):
+    """Prompt-lookup (n-gram) drafts for a speculative decode step, one launch: for every
+    active slot, ``win[s, 0] = tok0[s]`` (the token just sampled for position
+    ``p = lens[s]``) followed by up to ``k`` drafts, the tokens that followed the most recent
+    earlier occurrence of the sequence's last ``n`` tokens, the longest ``n`` in
+    ``[ngram_min, ngram_max]`` that occurs at all; ``n_win[s]`` = 1 + the number of drafts
+    (0 without a match, and never more than ``min(max_new - n_out, cap - p) - 1``). An
+    inactive slot, or one with ``p`` outside ``[0, cap)``, gets ``n_win = 0`` and keeps its
+    ``win`` row. Exact semantics: ``reference.spec_draft``.
+
+    ``tok0`` int64 [S], ``hist`` int32 [S, cap] (the request's tokens by absolute position;
+    only ``[0, p)`` is read), ``lens`` / ``n_out`` / ``max_new`` int32 [S], ``active`` uint8
+    [S], ``k`` in 1..8, ``1 <= ngram_min <= ngram_max <= 8``. ``win`` int64 [S, k + 1] and
+    ``n_win`` int32 [S] are written IN PLACE (allocated, ``win`` zeroed, when None) and
+    returned. Everything is read on the device and bounds-checked there: no host sync,
+    capturable.
+
+    HIP kernel (ops/csrc/spec.hip) for GPU tensors, the plain-loop reference otherwise."""
+    op = "spec_draft"
+    if not isinstance(tok0, torch.Tensor) or tok0.dim() != 1 or tok0.dtype != torch.int64 or \
+            tok0.shape[0] < 1:
+        raise ValueError(f"{op}: tok0 must be an int64 tensor of shape [S]")
+    S = tok0.shape[0]
+    k, ngram_min, ngram_max = int(k), int(ngram_min), int(ngram_max)
+    if not 1 <= k <= SPEC_MAX_DRAFTS:
+        raise ValueError(f"{op}: k must be in 1..{SPEC_MAX_DRAFTS}, got {k}")
+    if not 1 <= ngram_min <= ngram_max <= SPEC_MAX_NGRAM:
+        raise ValueError(f"{op}: need 1 <= ngram_min <= ngram_max <= {SPEC_MAX_NGRAM}, got "
+                         f"{ngram_min}, {ngram_max}")
+    _spec_table("hist", op, hist, S, tok0, torch.int32)
+    for name, t in (("lens", lens), ("n_out", n_out), ("max_new", max_new)):
+        _int_vec(name, op, t, S, tok0)
+    _int_vec("active", op, active, S, tok0, torch.uint8)
+    if win is None:
+        win = torch.zeros(S, k + 1, dtype=torch.int64, device=tok0.device)
+    if n_win is None:
+        n_win = torch.empty(S, dtype=torch.int32, device=tok0.device)
+    _spec_table("win", op, win, S, tok0, torch.int64, k + 1)
+    _int_vec("n_win", op, n_win, S, tok0)
+    if not _hip(tok0):
+        return ref.spec_draft(tok0, hist, lens, n_out, max_new, active, k, ngram_min, ngram_max,
+                              win, n_win)
+    if hist.shape[1] > (1 << 22):
+        raise ValueError(f"{op}: hist has more than {1 << 22} columns")
+    for name, t in (("win", win), ("n_win", n_win)):
+        if not t.is_contiguous():
+            raise ValueError(f"{op}: {name} is written in place and must be contiguous")
+    check(_lib.lib().ra_spec_draft(ptr(tok0.contiguous()), ptr(hist.contiguous()),
+                                   ptr(lens.contiguous()), ptr(n_out.contiguous()),
+                                   ptr(max_new.contiguous()), ptr(active.contiguous()), ptr(win),
+                                   ptr(n_win), S, hist.shape[1], k, ngram_min, ngram_max,
+                                   stream_ptr()), op)
+    return win, n_win
+
+
+def spec_accept(win, n_win, cand, logits_win, lens, n_out, max_new, active, out, hist, buf,
+                n_drafted, n_accepted, eos_token_id=None):
+    """The engine's bookkeeping after the verify pass of a speculative step, one launch, IN
+    PLACE: ``slot_advance`` for a window of tokens. ``cand[s, i]`` is the sampler's token for
+    position ``lens[s] + 1 + i``, drawn from the logits after ``win[s, i]``; a slot keeps
+    ``win[s, 0]`` and the drafts up to the first one the sampler disagrees with, ``m >= 1``
+    tokens, cut after the first ``eos_token_id`` and at ``max_new``. They go to
+    ``out[s, n_out ..]`` and ``hist[s, lens ..]``; ``n_out``, ``lens`` and the counters
+    ``n_drafted`` (+= n_win - 1) and ``n_accepted`` (+= m - 1) advance; the slot retires on
+    EOS or at ``max_new``, else ``buf[s] = logits_win[s, m - 1]``, the logits at its new
+    ``lens``. An active slot with ``n_win`` outside 1..k+1, or ``n_out`` / ``lens`` outside
+    ``[0, cap)``, retires without a write; every slot that is inactive afterwards gets
+    ``lens[s] = SLOT_INACTIVE``. Exact semantics: ``reference.spec_accept``.
+
+    ``win`` / ``cand`` int64 [S, k + 1], ``n_win`` / ``lens`` / ``n_out`` / ``max_new`` /
+    ``n_drafted`` / ``n_accepted`` int32 [S], ``active`` uint8 [S], ``logits_win``
+    [S, k + 1, Vp] and ``buf`` [S, Vp] of one dtype, ``out`` int64 [S, cap], ``hist`` int32
+    [S, cap], on one device. No host sync: capturable.
+
+    HIP kernel (ops/csrc/spec.hip; the logits row moves as 16-byte vectors when Vp is a
+    multiple of 8) for GPU tensors with bf16 logits, the plain-loop reference otherwise."""
+    op = "spec_accept"
+    if not isinstance(win, torch.Tensor) or win.dim() != 2 or win.dtype != torch.int64 or \
+            win.shape[0] < 1 or not 2 <= win.shape[1] <= SPEC_MAX_DRAFTS + 1:
+        raise ValueError(f"{op}: win must be an int64 tensor [S, k + 1], k in "
+                         f"1..{SPEC_MAX_DRAFTS}")
+    S, W = win.shape
+    _spec_table("cand", op, cand, S, win, torch.int64, W)
+    for name, t in (("n_win", n_win), ("lens", lens), ("n_out", n_out), ("max_new", max_new),
+                    ("n_drafted", n_drafted), ("n_accepted", n_accepted)):
+        _int_vec(name, op, t, S, win)
+    _int_vec("active", op, active, S, win, torch.uint8)
+    _spec_table("out", op, out, S, win, torch.int64)
+    _spec_table("hist", op, hist, S, win, torch.int32, out.shape[1])
+    if not isinstance(buf, torch.Tensor) or buf.dim() != 2 or buf.shape[0] != S or \
+            buf.shape[1] < 1 or not buf.dtype.is_floating_point or buf.device != win.device:
+        raise ValueError(f"{op}: buf must be a floating tensor [{S}, Vp] on {win.device}")
+    Vp = buf.shape[1]
+    if not isinstance(logits_win, torch.Tensor) or logits_win.shape != (S, W, Vp) or \
+            logits_win.dtype != buf.dtype or logits_win.device != win.device:
+        raise ValueError(f"{op}: logits_win must be a {buf.dtype} tensor [{S}, {W}, {Vp}] on "
+                         f"{win.device}")
+    eos = -1 if eos_token_id is None else int(eos_token_id)
+    if not (_hip(win) and buf.dtype == torch.bfloat16):
+        return ref.spec_accept(win, n_win, cand, logits_win, lens, n_out, max_new, active, out,
+                               hist, buf, n_drafted, n_accepted, eos)
+    if out.shape[1] > (1 << 22):
+        raise ValueError(f"{op}: out has more than {1 << 22} columns")
+    for name, t in (("lens", lens), ("n_out", n_out), ("active", active), ("out", out),
+                    ("hist", hist), ("buf", buf), ("n_drafted", n_drafted),
+                    ("n_accepted", n_accepted)):
+        if not t.is_contiguous():
+            raise ValueError(f"{op}: {name} is written in place and must be contiguous")
+    check(_lib.lib().ra_spec_accept(ptr(win.contiguous()), ptr(n_win.contiguous()),
+                                    ptr(cand.contiguous()), ptr(logits_win.contiguous()),
+                                    ptr(lens), ptr(n_out), ptr(max_new.contiguous()), ptr(active),
+                                    ptr(out), ptr(hist), ptr(buf), ptr(n_drafted),
+                                    ptr(n_accepted), S, out.shape[1], W - 1, Vp, eos,
+                                    stream_ptr()), op)
+
+
 SAMPLE_MAX_VOCAB = 1 << 18  # ops/csrc/sample.hip kMaxV (checked against the library)
 
 

@@ -202,6 +202,103 @@ def slot_advance(tok, lens, n_out, max_new, active, out, eos_token_id=None):
     lens.masked_fill_(~stay, SLOT_INACTIVE)
 
 
+def spec_draft(tok0, hist, lens, n_out, max_new, active, k, ngram_min, ngram_max, win, n_win):
+    """Prompt-lookup (n-gram) drafts of a speculative step (ops/csrc/spec.hip semantics): the
+    single definition of them, as plain loops. ``tok0`` int64 [S] is the token just sampled
+    for position ``p = lens[s]``, ``hist`` int32 [S, cap] the request's tokens by absolute
+    position (only ``[0, p)`` is read), ``lens`` / ``n_out`` / ``max_new`` int32 [S],
+    ``active`` uint8 [S]; ``win`` int64 [S, k + 1] and ``n_win`` int32 [S] are written IN PLACE.
+
+    An inactive slot, or one with ``p`` outside ``[0, cap)``, gets ``n_win = 0`` and keeps
+    its ``win`` row. Otherwise ``win[s, 0] = tok0[s]``; with ``seq = hist[s, :p] + [tok0]``,
+    ``L = p + 1`` and ``room = min(max_new - n_out, cap - p)``: for ``n = ngram_max`` down to
+    ``ngram_min`` with ``n <= L - 1``, the largest ``j`` with ``j + n <= L - 1`` and
+    ``seq[j : j+n] == seq[L-n : L]`` is looked for, and the first ``n`` with a match wins.
+    Then ``nd = min(k, room - 1)`` and draft i (1-based) is ``seq[q]``, ``q = j + n + i - 1``,
+    if ``q < L``, else draft ``q - L + 1``: the continuation runs on into the drafts. Without
+    a match ``nd = 0``. ``n_win = 1 + max(nd, 0)``. Reads the host."""
+    cap = hist.shape[1]
+    rows = zip(tok0.tolist(), lens.tolist(), n_out.tolist(), max_new.tolist(), active.tolist())
+    for s, (t0, p, n_o, mx, act) in enumerate(rows):
+        if not act or not 0 <= p < cap:
+            n_win[s] = 0
+            continue
+        seq = hist[s, :p].tolist() + [t0]
+        L = p + 1
+        start = None  # j + n of the winning match
+        for n in range(ngram_max, ngram_min - 1, -1):
+            if n > L - 1:
+                continue
+            suffix = seq[L - n:]
+            for j in range(L - 1 - n, -1, -1):
+                if seq[j: j + n] == suffix:
+                    start = j + n
+                    break
+            if start is not None:
+                break
+        nd = 0
+        if start is not None:
+            nd = max(min(k, min(mx - n_o, cap - p) - 1), 0)
+            for i in range(nd):
+                seq.append(seq[start + i])
+        win[s, : 1 + nd] = torch.tensor(seq[p:], dtype=win.dtype)
+        n_win[s] = 1 + nd
+    return win, n_win
+
+
+def spec_accept(win, n_win, cand, logits_win, lens, n_out, max_new, active, out, hist, buf,
+                n_drafted, n_accepted, eos_token_id=None):
+    """Acceptance of a speculative step (ops/csrc/spec.hip semantics): the single definition,
+    as a plain loop, everything IN PLACE. ``win`` / ``cand`` int64 [S, k + 1] (``cand[s, i]``:
+    the sampler's token for position ``p + 1 + i``, from the logits after ``win[s, i]``),
+    ``n_win`` int32 [S], ``logits_win`` [S, k + 1, Vp], ``lens`` / ``n_out`` / ``max_new`` /
+    ``n_drafted`` / ``n_accepted`` int32 [S], ``active`` uint8 [S], ``out`` int64 [S, cap],
+    ``hist`` int32 [S, cap], ``buf`` [S, Vp].
+
+    An active slot with ``1 <= n_win <= k + 1``, ``0 <= n_out < cap`` and ``0 <= p = lens[s]
+    < cap``: ``a`` is the largest ``i <= n_win - 1`` with ``win[s, j] == cand[s, j-1]`` for all
+    ``1 <= j <= i``. The tokens ``win[s, 0..a]`` are emitted, cut after the first
+    ``eos_token_id`` (which is emitted) and at ``max(1, min(max_new - n_out, cap - n_out,
+    cap - p))``: ``m >= 1`` tokens, stored at ``out[s, n_out ..]`` and ``hist[s, p ..]``;
+    ``n_out += m``, ``lens += m``, ``n_drafted += n_win - 1``, ``n_accepted += m - 1``. The
+    slot becomes inactive on EOS or when ``n_out >= max_new``; if it stays active,
+    ``buf[s] = logits_win[s, m-1]`` bitwise (the logits at the new ``lens[s]``). An active
+    slot with any other ``n_win`` / ``n_out`` / ``lens`` becomes inactive without a write.
+    Every slot that is inactive after that gets ``lens[s] = SLOT_INACTIVE``. Reads the host."""
+    W, cap = win.shape[1], out.shape[1]
+    eos = -1 if eos_token_id is None else int(eos_token_id)
+    for s in range(win.shape[0]):
+        act = bool(active[s])
+        if act:
+            nw, n, p, mx = int(n_win[s]), int(n_out[s]), int(lens[s]), int(max_new[s])
+            if not (1 <= nw <= W and 0 <= n < cap and 0 <= p < cap):
+                act = False
+            else:
+                w, c = win[s].tolist(), cand[s].tolist()
+                a = 0
+                while a + 1 < nw and w[a + 1] == c[a]:
+                    a += 1
+                toks = w[: min(a + 1, max(1, min(mx - n, cap - n, cap - p)))]
+                hit = eos >= 0 and eos in toks
+                if hit:
+                    toks = toks[: toks.index(eos) + 1]
+                m = len(toks)
+                out[s, n: n + m] = torch.tensor(toks, dtype=out.dtype)
+                hist[s, p: p + m] = torch.tensor(toks, dtype=torch.int64).to(hist.dtype)
+                n_out[s] = n + m
+                lens[s] = p + m
+                n_drafted[s] += nw - 1
+                n_accepted[s] += m - 1
+                if hit or n + m >= mx:
+                    act = False
+                else:
+                    buf[s] = logits_win[s, m - 1]
+            if not act:
+                active[s] = 0
+        if not act:
+            lens[s] = SLOT_INACTIVE
+
+
 def _lora_rows(y, x, a_stack, b_stack, idx):
     """The views and the per-row adapter choice both LoRA forms share: ``(y3, x3, A, B, ic,
     ok)`` with A, B the rows' adapters (a clamped id for the rows that have none)."""

@@ -208,7 +208,7 @@ class GPT2EngineServer:
 
     def __init__(self, config="small", state_dict_path=None, seed=0, slots=None,
                  eos_token_id=None, device=None, poll_every=None, prefixes=None,
-                 prefill_chunk=None, adapters=None, lora_rank=16):
+                 prefill_chunk=None, adapters=None, lora_rank=16, speculate=0, ngram=(2, 4)):
         import queue
         import threading
 
@@ -226,6 +226,7 @@ class GPT2EngineServer:
         self._lora_rank = int(lora_rank)
         self._aids = {}  # adapter name -> the engine's adapter slot
         self._prefill_chunk = prefill_chunk
+        self._speculate, self._ngram = speculate, ngram
         self._pids = {}  # prefix name -> the engine's prefix id
         ready = threading.Event()
         self._thread = threading.Thread(
@@ -259,7 +260,8 @@ class GPT2EngineServer:
                                        model.wte.device, model.wte.dtype)
             eng = GPT2Engine(model.eval(), slots=slots, eos_token_id=eos_token_id,
                              prefix_slots=len(self._prefixes),
-                             prefill_chunk=self._prefill_chunk, **kw)
+                             prefill_chunk=self._prefill_chunk, speculate=self._speculate,
+                             ngram=self._ngram, **kw)
             for i, (name, state) in enumerate(self._adapters.items()):
                 if not isinstance(state, dict):
                     state = torch.load(state, map_location="cpu")
@@ -388,7 +390,7 @@ class GPT2EngineServer:
 def build_gpt2_app(config="small", state_dict_path=None, seed=0, max_batch_size=8,
                    batch_wait_timeout_s=0.01, device=None, continuous=False, slots=None,
                    eos_token_id=None, prefixes=None, prefill_chunk=None, adapters=None,
-                   lora_rank=16):
+                   lora_rank=16, speculate=0, ngram=(2, 4)):
     """A Serve application around one ``GPT2Server`` replica (``serve.run`` it). ``config``
     names a ``GPT2Config`` preset; without ``state_dict_path`` the weights are the seeded
     random init. ``device`` None: the GPU assigned to the replica, else the CPU.
@@ -401,12 +403,14 @@ def build_gpt2_app(config="small", state_dict_path=None, seed=0, max_batch_size=
     (``{"name": path_or_state_dict, ...}``: low-rank adapters of rank up to ``lora_rank`` in
     the ``LoRAStack.load`` format, paths read with ``torch.load``), which a request names
     with ``"adapter": "name"``; a ``prefixes`` value may be ``{"tokens": [...], "adapter":
-    "name"}``."""
+    "name"}``. ``speculate=k`` (1..8; needs ``continuous=True`` too) turns on the engine's
+    speculative decoding with prompt-lookup drafts of the n-gram lengths ``ngram=(lo, hi)``:
+    the same tokens, up to k + 1 of them per device step."""
     if continuous:
         dep = deployment(GPT2EngineServer, name="GPT2EngineServer")
         return dep.bind(config, state_dict_path, seed, slots, eos_token_id, device, None,
-                        prefixes, prefill_chunk, adapters, lora_rank)
-    if prefixes or prefill_chunk is not None or adapters:
-        raise ValueError("prefixes, prefill_chunk and adapters need continuous=True")
+                        prefixes, prefill_chunk, adapters, lora_rank, speculate, ngram)
+    if prefixes or prefill_chunk is not None or adapters or speculate:
+        raise ValueError("prefixes, prefill_chunk, adapters and speculate need continuous=True")
     dep = deployment(GPT2Server, name="GPT2Server")
     return dep.bind(config, state_dict_path, seed, max_batch_size, batch_wait_timeout_s, device)
