@@ -36,7 +36,13 @@
 //
 // Schedule: the staggered two-group loop of gemm.hip (variant 0): per K-step
 // R0 | M0 | R1 | M1 with a barrier between slots, waves 4-7 one barrier behind waves 0-3,
-// so in every slot one wave of each SIMD issues MFMAs while its partner reads LDS.
+// so in every slot one wave of each SIMD issues MFMAs while its partner reads LDS. The
+// next K-step's tiles are staged at the top of each wave's R0 slot: 8 scalar-base DMA
+// pieces whose per-lane 32-bit byte offsets (row, swizzled column, ragged-edge clamp) are
+// computed once per workgroup; per K-step only two wave-uniform 64-bit bases advance, on
+// the scalar unit, so the staging holds no vector ALU instruction. ra_wgrad refuses strides
+// whose offsets would not fit 32 bits. Measurements, the compiled-loop audit and the
+// placements of the pieces that were tried and dropped: profiles/r15/wgrad_staging.md.
 //
 // Reference: torch autograd's linear backward (dW = grad_output^T @ input), the op the
 // reference's Ray Train GPT-2 benchmark runs through DDP
@@ -76,18 +82,20 @@ __device__ __forceinline__ int xcd_remap_w(int b, int G) {
 // builtin, hipcc cannot tell the DMA's LDS write from the fragment reads of the other
 // stage buffer and drains the prefetch with s_waitcnt vmcnt(0) in front of them; as asm it
 // is ordered only by the loop's explicit vmcnt + barrier protocol. M0 saved and restored.
-__device__ __forceinline__ void glds16_w(const bf16_t* gsrc, bf16_t* ldst) {
+// Scalar-base form: source = sbase (wave-uniform, SGPR pair) + zero-extended 32-bit byte
+// offset `voff` per lane, so a K-step's staging needs no vector address arithmetic.
+__device__ __forceinline__ void glds16_w(unsigned voff, const bf16_t* sbase, bf16_t* ldst) {
   const unsigned la = __builtin_amdgcn_readfirstlane(
       (unsigned)(unsigned long)(__attribute__((address_space(3))) void*)ldst);
   unsigned saved;
   asm volatile(
       "s_mov_b32 %0, m0\n\t"
-      "s_mov_b32 m0, %2\n\t"
+      "s_mov_b32 m0, %3\n\t"
       "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %1, off\n\t"
+      "global_load_lds_dwordx4 %1, %2\n\t"
       "s_mov_b32 m0, %0"
       : "=&s"(saved)
-      : "v"(gsrc), "s"(la)
+      : "v"(voff), "s"(sbase), "s"(la)
       : "memory");
 }
 
@@ -108,9 +116,12 @@ struct WgradArgs {
 };
 
 // One operand tile (64 token rows x 256 columns from col0) -> swizzled lane-linear image.
-// Wave w stages rows 8w .. 8w+7 (4 DMA instructions of 2 rows each).
-__device__ __forceinline__ void stage_t(bf16_t* img, const bf16_t* __restrict__ g, long ld,
-                                        int col0, int cols, long t0, int w, int lane) {
+// Wave w stages rows 8w .. 8w+7 (4 DMA pieces of 2 rows each). A lane's source offset
+// within a K-step, (row * ld + column) * 2 bytes with the source-side swizzle and the
+// ragged-edge clamp folded in, does not depend on the K-step: computed once per workgroup.
+// Below 2^32 by ra_wgrad's argument check.
+__device__ __forceinline__ void stage_offsets(unsigned (&off)[4], long ld, int col0, int cols,
+                                              int w, int lane) {
   const int rsub = lane >> 5, cp = lane & 31;
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
@@ -118,8 +129,7 @@ __device__ __forceinline__ void stage_t(bf16_t* img, const bf16_t* __restrict__ 
     const int c = cp ^ (2 * fsw(r));
     int col = col0 + 8 * c;
     col = col < cols ? col : cols - 8;  // ragged edge: clamp (outputs masked at the store)
-    const bf16_t* src = g + (t0 + r) * ld + col;
-    glds16_w(src, img + (8 * w + 2 * j) * kTile);
+    off[j] = (unsigned)((r * ld + col) * 2);
   }
 }
 
@@ -158,11 +168,22 @@ __device__ __forceinline__ void wgrad_mainloop(bf16_t* lds, const TileJob& j,
     yoff[nb] = row_off + 8 * ((2 * m + (p >> 1)) ^ (2 * fl));
   }
 
-  auto stage = [&](int buf, int ks) __attribute__((always_inline)) {
-    bf16_t* img = lds + buf * kStage;
-    const long t0 = (long)ks * kT;
-    stage_t(img, j.x, j.ldx, j.k0, j.K, t0, w, lane);
-    stage_t(img + kImg, j.dy, j.ldy, j.n0, j.N, t0, w, lane);
+  // staging: a wave's 8 DMA pieces per K-step (4 of X, 4 of dY). The per-lane byte offsets
+  // hold for the whole loop; the K-step enters through the wave-uniform bases only, which
+  // advance by 64 rows per staged step on the scalar unit: no vector ALU work per step.
+  unsigned sxo[4], syo[4];
+  stage_offsets(sxo, j.ldx, j.k0, j.K, w, lane);
+  stage_offsets(syo, j.ldy, j.n0, j.N, w, lane);
+  const bf16_t* xb = j.x + (long)j.s_beg * kT * j.ldx;
+  const bf16_t* yb = j.dy + (long)j.s_beg * kT * j.ldy;
+  auto stage = [&](int buf) __attribute__((always_inline)) {  // the next unstaged token step
+    bf16_t* img = lds + buf * kStage + 8 * w * kTile;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) glds16_w(sxo[i], xb, img + 2 * i * kTile);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) glds16_w(syo[i], yb, img + kImg + 2 * i * kTile);
+    xb += kT * j.ldx;
+    yb += kT * j.ldy;
   };
   auto barrier = []() __attribute__((always_inline)) {
     asm volatile("" ::: "memory");
@@ -231,15 +252,27 @@ __device__ __forceinline__ void wgrad_mainloop(bf16_t* lds, const TileJob& j,
     }
   };
 
+  // Staging protocol (the invariant any placement of the pieces has to keep). Step s is
+  // read from buffer s & 1; the pieces of step s + 1 go to the other buffer, which held
+  // step s - 1.
+  //   - Issue: only after the barrier that ends group 0's step s - 1. The last reads of
+  //     that buffer, group 1's R1 of step s - 1, retired (lgkmcnt(0)) before that barrier.
+  //     Both groups' loop tops lie behind it: group 1's is one barrier later.
+  //   - Landing: every wave waits vmcnt(0) on its own pieces before the barrier in front of
+  //     group 0's R0 of step s + 1, the first read of the new image: group 0 after its M1
+  //     cluster, group 1 after its R1 reads, which end at that same barrier.
+  // All 8 pieces stay at the top of the wave's R0 slot, ahead of its LDS reads. Spreading
+  // them over the read slots or interleaving them with the MFMAs measured slower, and so
+  // did issuing them behind the slot's LDS reads (profiles/r15/wgrad_staging.md).
   if (total > 0) {
-    stage(0, j.s_beg);
+    stage(0);
     wait_vm_w<0>();
   }
   barrier();
   if (g1) barrier();
   for (int s = 0; s < total; ++s) {
     const int buf = s & 1;
-    if (s + 1 < total) stage(buf ^ 1, j.s_beg + s + 1);  // buffer of step s-1: reads retired
+    if (s + 1 < total) stage(buf ^ 1);
     read_frags(buf, 0);
     barrier();
     mfma_cluster();
@@ -363,6 +396,9 @@ __global__ __launch_bounds__(kThreads) void wgrad_kernel(WgradArgs a) {
 
 int g_cus_w = 0;
 
+// (64 ld + cols) * 2 <= 2^32, without overflowing on a huge ld
+bool stage_offsets_fit(long ld, int cols) { return ld >= 0 && ld <= ((1L << 31) - cols) / kT; }
+
 }  // namespace
 
 // dW[N][K] (+)= dY[:M]^T X[:M] (+ bias gradient) over the first M - M % 64 tokens.
@@ -375,6 +411,8 @@ RA_EXPORT int ra_wgrad(const void* dy, long ldy, const void* x, long ldx, int M,
   if (M < 64 || N <= 0 || K <= 0 || N % 8 || K % 8 || ldy % 8 || ldx % 8 || S < 1)
     return hipErrorInvalidValue;
   if ((flags & 4) && bias_out == nullptr) return hipErrorInvalidValue;
+  // the staging offsets are unsigned 32-bit bytes: every lane's is below (64 ld + cols) * 2
+  if (!stage_offsets_fit(ldy, N) || !stage_offsets_fit(ldx, K)) return hipErrorInvalidValue;
   WgradArgs a;
   a.dy = (const bf16_t*)dy;
   a.x = (const bf16_t*)x;

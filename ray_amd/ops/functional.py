@@ -304,6 +304,11 @@ def _wgrad_partials(dy2, x2, S, M, N, K):
                      out_dtype=torch.float32)
 
 
+def _wgrad_offsets_fit(ld: int, cols: int) -> bool:
+    """ra_wgrad's staging offsets are unsigned 32-bit bytes: (64 ld + cols) * 2 <= 2^32."""
+    return 0 <= ld and (64 * ld + cols) * 2 <= 1 << 32
+
+
 def _wgrad_hip_ok(dy2, x2, sink, bias_sink=None) -> bool:
     M, N = dy2.shape
     K = x2.shape[1]
@@ -311,6 +316,7 @@ def _wgrad_hip_ok(dy2, x2, sink, bias_sink=None) -> bool:
             and M >= 64 and N % 8 == 0 and K % 8 == 0
             and dy2.stride(1) == 1 and x2.stride(1) == 1
             and dy2.stride(0) % 8 == 0 and x2.stride(0) % 8 == 0
+            and _wgrad_offsets_fit(dy2.stride(0), N) and _wgrad_offsets_fit(x2.stride(0), K)
             and dy2.data_ptr() % 16 == 0 and x2.data_ptr() % 16 == 0
             and sink.is_contiguous() and sink.numel() == N * K
             and sink.dtype in (torch.float32, torch.bfloat16) and sink.data_ptr() % 16 == 0
@@ -319,6 +325,7 @@ def _wgrad_hip_ok(dy2, x2, sink, bias_sink=None) -> bool:
                                        and bias_sink.numel() == N)))
 
 
+# (where the kernel's time goes and how its staging was measured: profiles/r15/wgrad_staging.md)
 def wgrad_accumulate(dy2, x2, sink, bias_sink=None, accumulate=True):
     """sink[N, K] (+)= dy2[M, N]^T @ x2[M, K] and, with ``bias_sink``, bias_sink[N] (+)=
     colsum(dy2) — the hand-written CDNA4 weight-gradient kernel (ops/csrc/wgrad.hip: both
