@@ -177,7 +177,7 @@ class _SeededSampler:
     and a token then costs one replay."""
 
     def __init__(self, model, cache, logits, out, temperature, top_k, top_p, seeds, eos,
-                 adapters=None):
+                 adapters=None, logprobs=None):
         cfg = model.cfg
         dev = out.device
         B = out.shape[0]
@@ -192,6 +192,12 @@ class _SeededSampler:
         self.seeds = torch.tensor(seeds, dtype=torch.int64, device=dev)
         self.done = torch.zeros(B, dtype=torch.uint8, device=dev)
         self.col = torch.zeros(1, 1, dtype=torch.long, device=dev)
+        # logprobs=n: the tables rf.token_logprobs fills at column ``col`` (None: no such call)
+        self.lp = None
+        if logprobs is not None:
+            self.top_n = logprobs
+            self.lp = _logprob_tables(B, out.shape[1], logprobs, dev)
+            self.cols = torch.zeros(B, dtype=torch.int32, device=dev)
         self.tok = None  # the sampler's output (inside a capture: the graph's static buffer)
         self.graph = None
 
@@ -201,11 +207,16 @@ class _SeededSampler:
                                self.seeds, self.cache.lens, done=self.done,
                                eos_token_id=self.eos, validate=False)
         self.out.scatter_(1, self.col.expand(self.out.shape[0], 1), tok.unsqueeze(1))
+        if self.lp is not None:
+            rf.token_logprobs(self.logits, tok, self.top_n, out=self.lp, rows=self.cache.rows,
+                              cols=self.cols)
         return tok
 
     def _step(self):
         self.tok = self._draw()
         self.col += 1
+        if self.lp is not None:
+            self.cols += 1
         self.model.decode_step(self.tok, self.cache, out=self.buf, adapters=self.adapters)
 
     def draw_last(self):
@@ -220,6 +231,20 @@ class _SeededSampler:
             self._step()
         else:
             self.graph.replay()
+
+
+def _logprob_tables(rows, cap, top_n, device):
+    """The ``out=`` tables of ``rf.token_logprobs``: ``(lp fp32 [rows, cap], top_ids int32
+    [rows, cap, top_n], top_lp fp32 [rows, cap, top_n])``, filled with (NaN, -1, NaN)."""
+    return (torch.full((rows, cap), float("nan"), dtype=torch.float32, device=device),
+            torch.full((rows, cap, top_n), -1, dtype=torch.int32, device=device),
+            torch.full((rows, cap, top_n), float("nan"), dtype=torch.float32, device=device))
+
+
+def _checked_top_n(name, n):
+    if isinstance(n, bool) or not isinstance(n, int) or not 0 <= n <= rf.LOGPROB_MAX_TOP:
+        raise ValueError(f"{name} must be an int in 0..{rf.LOGPROB_MAX_TOP}, got {n!r}")
+    return n
 
 
 def _per_row(name, value, default, B, cast):
@@ -490,6 +515,11 @@ class GPT2(nn.Module):
     def _prefill(self, idx, lens, store, adapters=None):
         """The prompt pass of ``prefill`` / ``prefill_into``: ``store(i, qkv)`` takes layer
         i's packed c_attn output [B, Tp, 3, H, hd] (Tp >= T: the padded width)."""
+        return self._last_logits(self._prompt_pass(idx, store, adapters), lens)
+
+    def _prompt_pass(self, idx, store, adapters=None):
+        """``idx`` [B, T] through the layers with causal (flash) attention: ``ln_f`` of the
+        result, [B, Tp, C]. ``store`` as in ``_prefill`` (None: nothing is kept)."""
         cfg = self.cfg
         B, T = idx.shape
         H, hd = cfg.n_head, cfg.n_embd // cfg.n_head
@@ -501,11 +531,11 @@ class GPT2(nn.Module):
 
         def attend(i, qkv):
             qkv = qkv.view(B, Tp, 3, H, hd)
-            store(i, qkv)
+            if store is not None:
+                store(i, qkv)
             return rf.causal_attention_qkv(qkv).reshape(B, Tp, cfg.n_embd)
 
-        h = self._layers(rf.embedding(idx, self.wte, self.wpe), attend, adapters)
-        return self._last_logits(h, lens)
+        return self._layers(rf.embedding(idx, self.wte, self.wpe), attend, adapters)
 
     @torch.no_grad()
     def decode_step(self, tok, cache: KVCache, out=None, adapters=None):
@@ -545,7 +575,7 @@ class GPT2(nn.Module):
     @torch.no_grad()
     def generate(self, idx, max_new_tokens, *, lens=None, temperature=0.0, top_k=None,
                  top_p=None, seeds=None, eos_token_id=None, generator=None, graph=False,
-                 adapters=None):
+                 adapters=None, logprobs=None):
         """Autoregressive generation with a KV cache: ``idx`` [B, T] prompts, right-padded
         to a common length with true lengths ``lens`` (default: all T). Returns the new
         tokens [B, max_new_tokens] (int64). ``temperature`` 0 is greedy, otherwise samples
@@ -564,18 +594,20 @@ class GPT2(nn.Module):
 
         ``adapters`` (an int, or one per row; -1 or None: the base model) names each row's
         adapter of the attached ``LoRAStack`` (``attach_lora``); the prompt pass and every
-        step apply it, inside the captured graph too."""
+        step apply it, inside the captured graph too.
+
+        ``logprobs=n`` (0..``rf.LOGPROB_MAX_TOP``; None, the default: the call as above):
+        returns ``(tokens, lp fp32 [B, max_new_tokens], top_ids int32 [B, max_new_tokens, n],
+        top_lp fp32 [B, max_new_tokens, n])``: the log-probability of every emitted token
+        under the logits it was drawn from and the n most likely tokens there with theirs
+        (``rf.token_logprobs``; the model's own distribution, whatever the sampling
+        parameters). On every path; with ``seeds=`` and ``graph=True`` the call is captured
+        with the step and a token still costs one replay."""
         cfg = self.cfg
         B, T = idx.shape
-        ad = None
-        if adapters is not None:
-            if self.lora is None:
-                raise ValueError("adapters given, but no adapter stack is attached: "
-                                 "attach_lora")
-            ad_l = _per_row("adapters", adapters, -1, B, int)
-            if any(not -1 <= v < self.lora.n_adapters for v in ad_l):
-                raise ValueError(f"adapters must be -1 or in [0, {self.lora.n_adapters})")
-            ad = torch.tensor(ad_l, dtype=torch.int32).to(idx.device)
+        if logprobs is not None:
+            _checked_top_n("logprobs", logprobs)
+        ad = self._adapter_tensor(adapters, B, idx.device)
         if seeds is None:
             if top_p is not None:
                 raise ValueError("top_p needs the device sampler: pass seeds=")
@@ -617,7 +649,9 @@ class GPT2(nn.Module):
         out = torch.empty(B, max_new_tokens, dtype=torch.long, device=dev)
         if seeds is not None:
             eos = None if eos_token_id is None else int(eos_token_id)
-            step = _SeededSampler(self, cache, logits, out, temps, ks, ps, seeds_l, eos, ad)
+            step = _SeededSampler(self, cache, logits, out, temps, ks, ps, seeds_l, eos, ad,
+                                  logprobs)
+            res = out if logprobs is None else (out,) + step.lp
             if max_new_tokens > 1:
                 step()
                 if graph:
@@ -627,19 +661,23 @@ class GPT2(nn.Module):
                     step.capture()
                     for _ in range(max_new_tokens - 1):
                         step()
-                    return out
+                    return res
                 for _ in range(max_new_tokens - 2):
                     step()
             step.draw_last()
-            return out
+            return res
         done = torch.zeros(B, dtype=torch.bool, device=dev)
         step = None
+        lp = None if logprobs is None else _logprob_tables(B, max_new_tokens, logprobs, dev)
         for t in range(max_new_tokens):
             tok = self._pick(logits, float(temperature), top_k, generator)
             if eos_token_id is not None:
                 tok = torch.where(done, torch.full_like(tok, eos_token_id), tok)
                 done |= tok == eos_token_id
             out[:, t] = tok
+            if lp is not None:
+                for table, got in zip(lp, rf.token_logprobs(logits, tok, logprobs)):
+                    table[:, t] = got
             if t + 1 == max_new_tokens:
                 break
             if not graph or t == 0:
@@ -649,7 +687,68 @@ class GPT2(nn.Module):
                 if step is None:
                     step = _GraphedStep(self, cache, tok, ad)
                 logits = step(tok)
-        return out
+        return out if lp is None else (out,) + lp
+
+    score_chunk = 1024  # rows of logits per LM-head chunk of ``score``
+
+    @torch.no_grad()
+    def score(self, idx, lens=None, top_n=0, adapters=None):
+        """Teacher-forced scoring: ``lp`` fp32 [B, T] with ``lp[b, t]`` the log-probability of
+        ``idx[b, t]`` given ``idx[b, :t]`` under the model's own distribution; position 0 and
+        the positions ``>= lens[b]`` (``idx`` is right-padded, default: all T) are NaN. With
+        ``top_n`` in 1..``rf.LOGPROB_MAX_TOP`` returns ``(lp, top_ids int32 [B, T, top_n],
+        top_lp fp32 [B, T, top_n])``, the most likely tokens at every position with theirs
+        (ids -1 and NaN where ``lp`` is NaN). ``adapters`` as in ``generate``.
+
+        One pass through the layers with causal (flash) attention, no cache, no host sync.
+        The LM head runs over ``score_chunk`` = 1024 of the B * (T - 1) rows at a time and
+        ``rf.token_logprobs`` puts each chunk's results in place, so the logits buffer is
+        bounded by 1024 x padded_vocab elements (103 MB of bf16 for GPT-2's 50304) whatever
+        B and T."""
+        cfg = self.cfg
+        if idx.dim() != 2 or idx.shape[0] < 1 or idx.shape[1] < 1:
+            raise ValueError("score needs idx [B, T] with B, T >= 1")
+        B, T = idx.shape
+        if T > cfg.n_positions:
+            raise ValueError(f"T ({T}) exceeds n_positions ({cfg.n_positions})")
+        _checked_top_n("top_n", top_n)
+        dev = idx.device
+        if lens is None:
+            lens = torch.full((B,), T, dtype=torch.int32, device=dev)
+        else:
+            lens = torch.as_tensor(lens, device=dev).to(torch.int32)
+            if lens.shape != (B,):
+                raise ValueError(f"lens must have shape [{B}]")
+        ad = self._adapter_tensor(adapters, B, dev)
+        out = _logprob_tables(B, T, top_n, dev)
+        N = B * (T - 1)
+        if N:
+            h = self._prompt_pass(idx, None, ad)[:, : T - 1].reshape(N, cfg.n_embd)
+            tok = idx[:, 1:].reshape(N)
+            rows = torch.arange(B, dtype=torch.int32, device=dev).repeat_interleave(T - 1)
+            cols = torch.arange(1, T, dtype=torch.int32, device=dev).repeat(B)
+            active = (cols < lens[rows.long()]).to(torch.uint8)
+            chunk = min(N, self.score_chunk)
+            buf = torch.empty(chunk, cfg.padded_vocab, device=dev, dtype=h.dtype)
+            for s in range(0, N, chunk):
+                e = min(N, s + chunk)
+                logits = torch.mm(h[s:e], self.wte.t(), out=buf[: e - s])[:, : cfg.vocab_size]
+                rf.token_logprobs(logits, tok[s:e], top_n, out=out, rows=rows[s:e],
+                                  cols=cols[s:e], active=active[s:e])
+        return out if top_n else out[0]
+
+    def _adapter_tensor(self, adapters, B, device):
+        """``generate``'s ``adapters`` (None, an int or one per row) as int32 [B] on
+        ``device``, or None."""
+        if adapters is None:
+            return None
+        if self.lora is None:
+            raise ValueError("adapters given, but no adapter stack is attached: "
+                             "attach_lora")
+        ad_l = _per_row("adapters", adapters, -1, B, int)
+        if any(not -1 <= v < self.lora.n_adapters for v in ad_l):
+            raise ValueError(f"adapters must be -1 or in [0, {self.lora.n_adapters})")
+        return torch.tensor(ad_l, dtype=torch.int32).to(device)
 
     def flops_per_token(self, T: int) -> float:
         """6N + 12·L·H·hd·T (PaLM appendix B convention), training FLOPs per token."""

@@ -78,6 +78,18 @@ for the others: the hook for a draft model. Memory safety does not depend on tha
 contract (every kernel checks its bounds), the tokens do. ``spec_stats()`` reports how
 many drafts were proposed and how many accepted.
 
+Log-probabilities (``logprobs=N``, 0..8; None, the default, is the engine without them: no
+buffer, no extra op, 3-tuple events): three more fixed-address tables, ``lp_hist``
+[S, max_len] and the top-N ids and values beside it, and ONE more call in the captured
+step, ``rf.token_logprobs`` between the sampler and ``rf.slot_advance`` with ``rows =
+cache.rows``, ``cols = n_out``, ``active = active``: the entry lands at the output index of
+the token ``slot_advance`` is about to store. The speculative step makes two calls before
+``rf.spec_accept``: ``tok0`` at ``n_out``, and the window's ``cand`` at ``n_out + 1 + j``
+for ``j < n_win``. ``submit(..., logprobs=m)``, m <= N, makes the request's events carry
+them; a poll is still one download. A request's entries are those of ``generate(...,
+seeds=[seed], logprobs=m)`` on it alone, cut after the first EOS, with prefixes, chunked
+prefill, adapters, ``cancel`` and every ``speculate``.
+
 Single-threaded by contract: every call comes from one thread."""
 
 from __future__ import annotations
@@ -85,6 +97,7 @@ from __future__ import annotations
 import collections
 import math
 
+import numpy as np
 import torch
 
 from ray_amd.models.gpt2 import GPT2, KVCache
@@ -94,21 +107,22 @@ from ray_amd.ops.graph_lock import CapturedStep
 
 class _Request:
     __slots__ = ("rid", "tokens", "max_new", "temperature", "top_k", "top_p", "seed", "pid",
-                 "adapter")
+                 "adapter", "logprobs")
 
     def __init__(self, rid, tokens, max_new, temperature, top_k, top_p, seed, pid=None,
-                 adapter=-1):
+                 adapter=-1, logprobs=None):
         # tokens: the whole prompt (the prefix's tokens included); pid: the prefix it names
         self.rid, self.tokens, self.max_new = rid, tokens, max_new
         self.temperature, self.top_k, self.top_p, self.seed = temperature, top_k, top_p, seed
         self.pid = pid
         self.adapter = adapter  # -1: the base model
+        self.logprobs = logprobs  # None: the request reports none; else its top-n width
 
 
 class GPT2Engine:
     def __init__(self, model: GPT2, slots=8, max_len=None, eos_token_id=None, graph=None,
                  poll_every=8, prefix_slots=0, prefill_chunk=None, lora=None, speculate=0,
-                 ngram=(2, 4), drafter=None):
+                 ngram=(2, 4), drafter=None, logprobs=None):
         cfg = model.cfg
         dev = model.wte.device
         S = int(slots)
@@ -132,6 +146,10 @@ class GPT2Engine:
             raise ValueError(f"ngram needs 1 <= min <= max <= {rf.SPEC_MAX_NGRAM}, got {ngram!r}")
         if drafter is not None and not speculate:
             raise ValueError("a drafter needs speculate >= 1")
+        if logprobs is not None and (isinstance(logprobs, bool) or not isinstance(logprobs, int)
+                                     or not 0 <= logprobs <= rf.LOGPROB_MAX_TOP):
+            raise ValueError(f"logprobs must be None or an int in 0..{rf.LOGPROB_MAX_TOP}, got "
+                             f"{logprobs!r}")
         if graph is None:
             graph = dev.type == "cuda"
         if graph and dev.type != "cuda":
@@ -181,6 +199,19 @@ class GPT2Engine:
                 self._drafter = self._ngram_drafter
         # a poll carries what poll_every steps can emit per slot
         self._ar = torch.arange(self.poll_every * (speculate + 1), device=dev).unsqueeze(0)
+        self.logprobs = logprobs
+        if logprobs is not None:
+            # entry [s, i] describes out[s, i]: written by rf.token_logprobs inside the step
+            self.lp_hist = torch.zeros(S, self.max_len, dtype=torch.float32, device=dev)
+            self.top_ids_hist = torch.full((S, self.max_len, logprobs), -1, dtype=torch.int32,
+                                           device=dev)
+            self.top_lp_hist = torch.zeros(S, self.max_len, logprobs, dtype=torch.float32,
+                                           device=dev)
+            self._lp_out = (self.lp_hist, self.top_ids_hist, self.top_lp_hist)
+            if speculate:
+                self._win_rows = self.cache.rows.repeat_interleave(speculate + 1)
+                self._win_idx = torch.arange(speculate + 1, dtype=torch.int32,
+                                             device=dev).unsqueeze(0)
 
         self._queue = collections.deque()
         self._slot_req = [None] * S  # the request running in each slot
@@ -209,6 +240,10 @@ class GPT2Engine:
             return self._spec_step()
         tok = rf.sample_logits(self.logits, self.temperature, self.top_k, self.top_p, self.seeds,
                                self.cache.lens, validate=False)
+        if self.logprobs is not None:
+            # the entry lands at the output index slot_advance is about to store tok at
+            rf.token_logprobs(self.logits, tok, self.logprobs, out=self._lp_out,
+                              rows=self.cache.rows, cols=self.n_out, active=self.active)
         rf.slot_advance(tok, self.cache.lens, self.n_out, self.max_new, self.active, self.out,
                         self.eos)
         self.model.decode_step(tok, self.cache, out=self.buf, adapters=self.adapter)
@@ -231,6 +266,18 @@ class GPT2Engine:
         cand = rf.sample_logits(self.logits_win.view(S * W, -1)[:, :V], temperature, top_k, top_p,
                                 seeds, (lens.unsqueeze(1) + self._win_offs).view(S * W),
                                 validate=False)
+        if self.logprobs is not None:
+            # tok0 goes to output index n_out; window row j holds the logits that decide
+            # output index n_out + 1 + j, and cand[s, j] is the token they give. What is
+            # written for drafts that are then rejected lies at or beyond the new n_out: a
+            # later step overwrites it, and a poll never reads it
+            rf.token_logprobs(self.logits, tok0, self.logprobs, out=self._lp_out,
+                              rows=self.cache.rows, cols=self.n_out, active=self.active)
+            live = (self._win_idx < n_win.unsqueeze(1)) & self.active.bool().unsqueeze(1)
+            rf.token_logprobs(self.logits_win.view(S * W, -1)[:, :V], cand, self.logprobs,
+                              out=self._lp_out, rows=self._win_rows,
+                              cols=(self.n_out.unsqueeze(1) + self._win_offs).view(S * W),
+                              active=live.to(torch.uint8).view(S * W))
         rf.spec_accept(win, n_win, cand.view(S, W), self.logits_win, lens, self.n_out,
                        self.max_new, self.active, self.out, self.hist, self.buf, self.n_drafted,
                        self.n_accepted, self.eos)
@@ -335,14 +382,23 @@ class GPT2Engine:
         self._prefix_free.append(self._prefixes.pop(pid)[0])
 
     def submit(self, tokens, max_new_tokens, temperature=0.0, top_k=None, top_p=None, seed=0,
-               prefix=None, adapter=None):
+               prefix=None, adapter=None, logprobs=None):
         """Queues a request and returns its id; a bad request raises ``ValueError`` and
         queues nothing. ``prefix``: an ``add_prefix`` id; ``tokens`` is then the non-empty
         continuation and the request's prompt is the prefix's tokens followed by it.
         ``adapter``: an int in [0, n_adapters) of the engine's stack (None: the base model,
         or the prefix's adapter when ``prefix`` is given; another adapter than the prefix's
-        is an error)."""
+        is an error). ``logprobs``: an int in 0..N on an engine built with ``logprobs=N``:
+        the request's events carry the log-probability of every token and the ``logprobs``
+        most likely tokens at its position (None: they carry none)."""
         tokens = self._checked_tokens(tokens, "request")
+        if logprobs is not None:
+            if self.logprobs is None:
+                raise ValueError("logprobs given, but the engine keeps none: logprobs=")
+            if isinstance(logprobs, bool) or not isinstance(logprobs, int) or \
+                    not 0 <= logprobs <= self.logprobs:
+                raise ValueError(f"logprobs must be an int in 0..{self.logprobs}, got "
+                                 f"{logprobs!r}")
         named = adapter is not None
         adapter = self._checked_adapter(adapter)
         if prefix is not None:
@@ -375,7 +431,7 @@ class GPT2Engine:
         rid = self._next_rid
         self._next_rid += 1
         self._queue.append(_Request(rid, tokens, max_new, temperature, top_k, top_p, seed,
-                                    prefix, adapter))
+                                    prefix, adapter, logprobs))
         return rid
 
     def cancel(self, rid):
@@ -509,6 +565,8 @@ class GPT2Engine:
         """One download, whatever S: per slot n_out, active and the (at most poll_every, times
         speculate + 1) tokens it produced since the last poll."""
         col = (self._seen.unsqueeze(1) + self._ar).clamp_(max=self.max_len - 1)
+        if self.logprobs is not None:
+            return self._poll_logprobs(col)
         host = torch.cat([self.n_out.long().unsqueeze(1), self.active.long().unsqueeze(1),
                           self.out.gather(1, col)], 1).tolist()
         self._seen.copy_(self.n_out)
@@ -525,11 +583,53 @@ class GPT2Engine:
                 events.append((r.rid, new, not act))
         return events
 
+    def _poll_logprobs(self, col):
+        """``_poll`` on an engine with logprobs: still one download, a float64 table (it holds
+        the token ids and the fp32 values exactly) of n_out, active and K = ``col.shape[1]``
+        columns each of tokens and logprobs and K * N each of top ids and top logprobs.
+        Events are ``(rid, new_tokens, finished, info)``."""
+        S, K, N = self.slots, col.shape[1], self.logprobs
+        colN = col.unsqueeze(2).expand(S, K, N)
+        f64 = torch.float64
+        host = torch.cat([self.n_out.to(f64).unsqueeze(1), self.active.to(f64).unsqueeze(1),
+                          self.out.gather(1, col).to(f64), self.lp_hist.gather(1, col).to(f64),
+                          self.top_ids_hist.gather(1, colN).to(f64).view(S, K * N),
+                          self.top_lp_hist.gather(1, colN).to(f64).view(S, K * N)], 1)
+        host = host.cpu().numpy()
+        self._seen.copy_(self.n_out)
+        head = host[:, :2].astype(np.int64).tolist()
+        ids0, lps0 = 2 + 2 * K, 2 + 2 * K + K * N
+        events = []
+        for s, r in enumerate(self._slot_req):
+            if r is None or self._fill[s] is not None:  # filling: inactive, not finished
+                continue
+            n, act = head[s]
+            k = n - self._seen_host[s]
+            row = host[s]  # only the k new columns of each block become Python objects
+            new = row[2: 2 + k].astype(np.int64).tolist()
+            self._seen_host[s] = n
+            if not act:
+                self._slot_req[s] = None
+            if not (new or not act):
+                continue
+            info = None
+            if r.logprobs is not None:
+                m = r.logprobs
+                info = {"logprobs": row[2 + K: 2 + K + k].tolist(),
+                        "top_ids": row[ids0: ids0 + k * N].reshape(k, N)[:, :m]
+                        .astype(np.int64).tolist(),
+                        "top_logprobs": row[lps0: lps0 + k * N].reshape(k, N)[:, :m].tolist()}
+            events.append((r.rid, new, not act, info))
+        return events
+
     def step(self):
         """Admits queued requests into free slots, feeds every filling slot one chunk of its
         prompt (the whole prompt without ``prefill_chunk``), runs ``poll_every`` device steps
         if any slot is decoding and polls: ``[(rid, new_tokens, finished), ...]`` for the
-        slots that produced tokens."""
+        slots that produced tokens. On an engine built with ``logprobs=N`` the events are
+        ``(rid, new_tokens, finished, info)``: ``info`` is None for a request that asked for
+        none, else ``{"logprobs": [...], "top_ids": [[...m]], "top_logprobs": [[...m]]}``,
+        aligned with ``new_tokens``."""
         self._admit()
         self._fill_round()
         if self.num_active == self.num_filling:
@@ -538,11 +638,20 @@ class GPT2Engine:
             self._run_step()
         return self._poll()
 
-    def run(self):
+    def run(self, logprobs=False):
         """Drives the engine until it is idle: ``{rid: tokens}`` of the requests that
-        produced tokens on the way."""
-        got = {}
+        produced tokens on the way. ``logprobs=True`` (an engine built with ``logprobs=N``):
+        ``{rid: (tokens, info)}``, ``info`` as in ``step`` over all the request's tokens."""
+        if logprobs and self.logprobs is None:
+            raise ValueError("logprobs=True, but the engine keeps none: logprobs=")
+        got, infos = {}, {}
         while self.has_work():
-            for rid, new, _ in self.step():
-                got.setdefault(rid, []).extend(new)
-        return got
+            for ev in self.step():
+                got.setdefault(ev[0], []).extend(ev[1])
+                if logprobs:
+                    info = infos.setdefault(ev[0], None if ev[3] is None else
+                                            {k: [] for k in ev[3]})
+                    if info is not None:
+                        for k, v in ev[3].items():
+                            info[k].extend(v)
+        return {rid: (toks, infos[rid]) for rid, toks in got.items()} if logprobs else got

@@ -134,6 +134,8 @@ _SIGS = {
     "ra_sample_logits_max_v": [],
     "ra_sample_logits": [c_void_p, c_long] + [c_void_p] * 6 + [c_int, c_void_p, c_int, c_int,
                                                                 c_void_p],
+    "ra_token_logprobs_max_top": [],
+    "ra_token_logprobs": [c_void_p, c_long] + [c_void_p] * 7 + [c_int] * 5 + [c_void_p],
     "ra_gemm_nt": [c_void_p, c_long, c_void_p, c_long, c_void_p, c_long, c_int, c_int, c_int,
                    c_int, c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_int, c_int,
                    c_void_p],

@@ -37,6 +37,7 @@
 // Histogram counters are replicated kRep times (lane & (kRep - 1)) so that the many logits
 // that share a high byte do not serialise on one LDS address.
 #include "common.h"
+#include "row_slots.h"
 
 namespace {
 
@@ -63,15 +64,6 @@ struct SampleArgs {
   int V;
 };
 
-__device__ __forceinline__ uint32_t key_of(uint32_t h) {  // h: bf16 bits
-  if (h == 0x8000u) h = 0;                                // -0 == +0
-  return (h & 0x8000u) ? (~h & 0xffffu) : (h | 0x8000u);
-}
-__device__ __forceinline__ float val_of(uint32_t key) {
-  const uint32_t h = (key & 0x8000u) ? (key & 0x7fffu) : (~key & 0xffffu);
-  return __uint_as_float(h << 16);
-}
-
 // floor(r * t / 2^24) for r < 2^24, t < 2^63, without a 128-bit product
 __device__ __forceinline__ u64 mul_shift24(u64 r, u64 t) {
   return r * (t >> 24) + ((r * (t & 0xffffffull)) >> 24);
@@ -95,33 +87,6 @@ __device__ __forceinline__ u64 shfl_up64(u64 v, int d) {
   return ((u64)hi << 32) | lo;
 }
 
-// A row as the aligned 16-byte slots that cover it. Slot j holds the elements with indices
-// j * 8 - off .. j * 8 - off + 7; those outside [0, V) (only in the first and the last
-// slot) are replaced by -inf, which weighs nothing, is never the maximum of a row that has
-// a finite logit and sits below every top-k or top-p threshold.
-struct Row {
-  const uint4* base;  // the row's start rounded down to 16 bytes
-  int off;            // elements between base and the row's start (0..7)
-  int V;
-  int nslots;
-  __device__ __forceinline__ uint4 load(int j) const {
-    uint4 u = base[j];
-    if (j == 0 || j == nslots - 1) {
-      uint32_t w[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const int i = j * 8 + e - off;
-        if (i < 0 || i >= V)
-          w[e >> 1] = (e & 1) ? ((w[e >> 1] & 0x0000ffffu) | 0xff800000u)
-                              : ((w[e >> 1] & 0xffff0000u) | 0x0000ff80u);
-      }
-      u = make_uint4(w[0], w[1], w[2], w[3]);
-    }
-    return u;
-  }
-};
-
-constexpr uint32_t kNegInf2 = 0xff80ff80u;  // two bf16 -inf
 constexpr int kBatch = 4;
 
 // Calls f(j, slot) for every slot of the row that this thread owns (j = tid, tid +
@@ -144,10 +109,6 @@ __device__ __forceinline__ void for_slots(const Row& row, const uint4* regs, F f
       for (int i = 0; i < kBatch; ++i) f(j + i * kThreads, u[i]);
     }
   }
-}
-
-__device__ __forceinline__ uint32_t key_of_val(float v) {
-  return key_of(__float_as_uint(v) >> 16);
 }
 
 struct Shared {

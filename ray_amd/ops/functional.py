@@ -1083,6 +1083,87 @@ def sample_logits(logits, temperature, top_k, top_p, seeds, steps, vocab_size=No
     return tok
 
 
+LOGPROB_MAX_TOP = 8  # ops/csrc/logprobs.hip kMaxTop (checked against the library)
+
+
+def token_logprobs(logits, tok, top_n=0, vocab_size=None, out=None, rows=None, cols=None,
+                   active=None):
+    """The log-probability of ``tok[b]`` (int64 [B]) under the softmax of row b of ``logits``
+    [B, Vs] (the first ``vocab_size or Vs`` columns count), and the ``top_n``
+    (0..``LOGPROB_MAX_TOP``) largest entries of the row with theirs, ordered by value
+    descending, then index ascending. Semantics: ``reference.token_logprobs``. The
+    distribution is the model's own (no temperature, top-k or top-p).
+
+    Without ``out``: returns ``(lp fp32 [B], top_ids int32 [B, top_n], top_lp fp32
+    [B, top_n])``. With ``out = (lp_hist fp32 [R, cap], ids_hist int32 [R, cap, top_n],
+    tlp_hist fp32 [R, cap, top_n])`` and ``rows`` / ``cols`` int32 [B] (``active`` uint8 [B]
+    optional): row b's results are written IN PLACE at ``[rows[b], cols[b]]``; a row with
+    ``active[b] == 0`` or an entry outside the tables writes nothing. Returns ``out``.
+
+    HIP kernel (ops/csrc/logprobs.hip: one launch, every index read on the device, no host
+    sync, capturable) for GPU tensors with bf16 logits of unit column stride and at most
+    ``SAMPLE_MAX_VOCAB`` columns; the rows may be a column slice of a wider buffer, read in
+    place. CPU tensors, other dtypes and wider vocabularies use the plain-torch reference."""
+    op = "token_logprobs"
+    if not isinstance(logits, torch.Tensor) or logits.dim() != 2:
+        raise ValueError(f"{op}: logits must be [B, V]")
+    B, Vs = logits.shape
+    V = Vs if vocab_size is None else int(vocab_size)
+    if B < 1 or V < 1 or V > Vs:
+        raise ValueError(f"{op}: vocab_size {V} does not fit logits {tuple(logits.shape)}")
+    if not logits.dtype.is_floating_point:
+        raise ValueError(f"{op}: logits must be floating point")
+    if isinstance(top_n, bool) or not isinstance(top_n, int) or \
+            not 0 <= top_n <= LOGPROB_MAX_TOP:
+        raise ValueError(f"{op}: top_n must be an int in 0..{LOGPROB_MAX_TOP}, got {top_n!r}")
+    _int_vec("tok", op, tok, B, logits, torch.int64)
+    dev = logits.device
+    if out is None:
+        if rows is not None or cols is not None or active is not None:
+            raise ValueError(f"{op}: rows, cols and active need out=")
+    else:
+        if not isinstance(out, (tuple, list)) or len(out) != 3:
+            raise ValueError(f"{op}: out must be (lp_hist, ids_hist, tlp_hist)")
+        lp_h, ids_h, tlp_h = out
+        if not isinstance(lp_h, torch.Tensor) or lp_h.dim() != 2 or lp_h.shape[0] < 1 or \
+                lp_h.shape[1] < 1 or lp_h.dtype != torch.float32 or lp_h.device != dev:
+            raise ValueError(f"{op}: lp_hist must be a float32 tensor [R, cap] on {dev}")
+        shape = tuple(lp_h.shape) + (top_n,)
+        for name, t, dt in (("ids_hist", ids_h, torch.int32), ("tlp_hist", tlp_h, torch.float32)):
+            if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.dtype != dt or \
+                    t.device != dev:
+                raise ValueError(f"{op}: {name} must be a {dt} tensor {list(shape)} on {dev}")
+        _int_vec("rows", op, rows, B, logits)
+        _int_vec("cols", op, cols, B, logits)
+        if active is not None:
+            _int_vec("active", op, active, B, logits, torch.uint8)
+        for name, t in (("lp_hist", lp_h), ("ids_hist", ids_h), ("tlp_hist", tlp_h)):
+            if not t.is_contiguous():
+                raise ValueError(f"{op}: {name} is written in place and must be contiguous")
+    if not (_hip(logits) and logits.dtype == torch.bfloat16 and V <= SAMPLE_MAX_VOCAB):
+        return ref.token_logprobs(logits, tok, top_n, V, out, rows, cols, active)
+    L = _lib.lib()
+    assert L.ra_token_logprobs_max_top() == LOGPROB_MAX_TOP
+    if logits.stride(1) != 1 or (B > 1 and logits.stride(0) < V):
+        logits = logits.contiguous()
+    if out is None:
+        res = (torch.empty(B, device=dev, dtype=torch.float32),
+               torch.empty(B, top_n, device=dev, dtype=torch.int32),
+               torch.empty(B, top_n, device=dev, dtype=torch.float32))
+        lp_h, ids_h, tlp_h = res
+        R, cap = B, 1
+    else:
+        res = out
+        R, cap = lp_h.shape
+        rows, cols = rows.contiguous(), cols.contiguous()
+        active = None if active is None else active.contiguous()
+    check(L.ra_token_logprobs(ptr(logits), max(logits.stride(0), V), ptr(tok.contiguous()),
+                              ptr(rows), ptr(cols), ptr(active), ptr(lp_h),
+                              ptr(ids_h) if top_n else None, ptr(tlp_h) if top_n else None,
+                              B, V, top_n, R, cap, stream_ptr()), op)
+    return res
+
+
 # --------------------------------------------------------------------- cross entropy
 class _CrossEntropy(torch.autograd.Function):
     @staticmethod

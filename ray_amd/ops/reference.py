@@ -428,6 +428,71 @@ def sample_logits(logits, temperature, top_k, top_p, seeds, steps, vocab_size=No
     return _sample_logits_u(logits, temperature, top_k, top_p, u, vocab_size)
 
 
+def _place_rows(dst, at, ok, val):
+    """``dst[at[b]] = val[b]`` along dim 0 for the rows with ``ok[b]``, IN PLACE; the other
+    rows land in a spare entry, so ``dst`` keeps their bytes. No host sync."""
+    n = dst.shape[0]
+    ext = torch.cat([dst, dst.new_zeros((1,) + tuple(dst.shape[1:]))])
+    ext.index_copy_(0, torch.where(ok, at, n), val.to(dst.dtype))
+    dst.copy_(ext[:n])
+
+
+def token_logprobs(logits, tok, top_n=0, vocab_size=None, out=None, rows=None, cols=None,
+                   active=None):
+    """Per-token log-probabilities (ops/csrc/logprobs.hip semantics): the single definition.
+
+    ``logits`` [B, Vs], of which the first ``V = vocab_size or Vs`` columns count; ``tok``
+    int64 [B]; ``top_n`` >= 0. Per row, with x the stored logits (the math runs in fp32, in
+    fp64 for fp64 logits):
+
+    * ``lse = max(x) + log(sum(exp(x - max(x))))`` and ``lp = x[tok] - lse``; a ``tok``
+      outside ``[0, V)`` gives NaN, a ``-inf`` logit ``-inf``.
+    * ``top_ids[j]``, ``top_lp[j]``, j < top_n: the ``top_n`` largest entries of x ordered by
+      value descending, then index ascending (a stable order, exact on the stored values,
+      -0 equal to +0), ``top_lp[j] = x[top_ids[j]] - lse``; ``(-1, -inf)`` for j >= V.
+
+    The distribution is the model's own: temperature, top-k and top-p play no part. NaN
+    logits and a row of all ``-inf`` are out of contract.
+
+    Without ``out``: returns dense ``(lp [B], top_ids int32 [B, top_n], top_lp [B, top_n])``.
+    With ``out = (lp_hist fp32 [R, cap], ids_hist int32 [R, cap, top_n], tlp_hist fp32
+    [R, cap, top_n])``, ``rows`` int32 [B], ``cols`` int32 [B] and optionally ``active``
+    uint8 [B]: row b's results go to ``[rows[b], cols[b]]`` IN PLACE; a row with
+    ``active[b] == 0``, ``rows[b]`` outside ``[0, R)`` or ``cols[b]`` outside ``[0, cap)``
+    writes nothing. Returns ``out``. No host sync."""
+    B, Vs = logits.shape
+    V = Vs if vocab_size is None else int(vocab_size)
+    ct = torch.float64 if logits.dtype == torch.float64 else torch.float32
+    x = logits[:, :V].to(ct)  # the stored values, exactly
+    m = x.max(-1, keepdim=True).values
+    lse = m + torch.log(torch.exp(x - m).sum(-1, keepdim=True))
+    t = tok.long()
+    ok = (t >= 0) & (t < V)
+    xt = x.gather(1, t.clamp(0, V - 1).unsqueeze(1))
+    lp = torch.where(ok, (xt - lse).squeeze(1), torch.full_like(lse.squeeze(1), float("nan")))
+    n, k = int(top_n), min(int(top_n), V)
+    ids = torch.full((B, n), -1, dtype=torch.int32, device=x.device)
+    tlp = torch.full((B, n), float("-inf"), dtype=ct, device=x.device)
+    if k:
+        xs, order = torch.sort(x, dim=-1, descending=True, stable=True)
+        ids[:, :k] = order[:, :k].to(torch.int32)
+        tlp[:, :k] = xs[:, :k] - lse
+    if out is None:
+        return lp, ids, tlp
+    lp_h, ids_h, tlp_h = out
+    R, cap = lp_h.shape
+    r, c = rows.long(), cols.long()
+    ok = (r >= 0) & (r < R) & (c >= 0) & (c < cap)
+    if active is not None:
+        ok = ok & active.bool()
+    at = r * cap + c
+    _place_rows(lp_h.view(R * cap), at, ok, lp)
+    if n:
+        _place_rows(ids_h.view(R * cap, n), at, ok, ids)
+        _place_rows(tlp_h.view(R * cap, n), at, ok, tlp)
+    return out
+
+
 def _f(x):
     return x.to(torch.promote_types(x.dtype, torch.float32))
 

@@ -34,7 +34,17 @@ start-up (each is prefilled once); a request may then carry ``"prefix": "name"``
 up to ``lora_rank``) into the engine at start-up; a request may then carry ``"adapter":
 "name"`` and shares its decode steps with requests of other adapters and of the base model.
 A prefix may be bound to an adapter: ``prefixes={"name": {"tokens": [...], "adapter":
-"name"}}``."""
+"name"}}``.
+
+Log-probabilities: a request may carry ``"logprobs": m`` (0..8). Its response gains
+``"logprobs": [...]``, the log-probability of every returned token under the model's own
+distribution (whatever the sampling parameters), and ``"top_logprobs": [[[id, lp], ... m],
+...]``, the m most likely tokens at every position with theirs; a streamed chunk carries the
+slice for its tokens, and a non-finite value is ``None`` (JSON has no ``-inf``). The static
+server routes such a batch through the device sampler, one ``generate(..., logprobs=max m)``
+call, each result cut to its own m. The continuous server needs ``build_gpt2_app(...,
+logprobs=N)``, which passes N to the engine; m above N, or m on an app built without it, is
+that request's error. A request without the field gets the response it always got."""
 
 from __future__ import annotations
 
@@ -56,6 +66,33 @@ def _pick_device(device):
         gpus = []
     # the raylet narrows the replica's visible devices to the ones it was assigned
     return torch.device("cuda", 0) if gpus and torch.cuda.is_available() else torch.device("cpu")
+
+
+def _request_logprobs(r, limit, hint=""):
+    """The request's checked ``"logprobs"`` (None: the field is absent) against ``limit``
+    (None: the server keeps none)."""
+    m = r.get("logprobs")
+    if m is None:
+        return None
+    if isinstance(m, bool) or not isinstance(m, int) or m < 0:
+        raise ValueError("logprobs must be an int >= 0")
+    if limit is None:
+        raise ValueError("'logprobs' needs build_gpt2_app(continuous=True, logprobs=N)")
+    if m > limit:
+        raise ValueError(f"logprobs ({m}) exceeds the server's {limit}{hint}")
+    return m
+
+
+def _finite(v):
+    return v if v == v and abs(v) != float("inf") else None
+
+
+def _logprob_fields(lp, ids, tlp, m):
+    """The response fields for one request's tokens: ``lp`` [n], ``ids`` / ``tlp`` [n][>= m]
+    as lists."""
+    return {"logprobs": [_finite(v) for v in lp],
+            "top_logprobs": [[[int(i), _finite(v)] for i, v in zip(ri[:m], rv[:m])]
+                             for ri, rv in zip(ids, tlp)]}
 
 
 class GPT2Server:
@@ -99,30 +136,45 @@ class GPT2Server:
                              "continuous=True, adapters=...)")
         return _request_params(self.model.cfg, self.seed, r)
 
-    def _run_sampled(self, reqs, params):
-        """One ragged generate call through the device sampler, every parameter per row."""
+    def _run_sampled(self, reqs, params, lps=None):
+        """One ragged generate call through the device sampler, every parameter per row.
+        ``lps`` (each request's ``logprobs`` or None; not all None): the call reports the
+        batch's widest and every result is a dict cut to its own."""
         lens = [p[0] for p in params]
         new = [p[1] for p in params]
         idx = torch.zeros(len(reqs), max(lens), dtype=torch.long)
         for b, r in enumerate(reqs):
             idx[b, : lens[b]] = torch.tensor(r["tokens"], dtype=torch.long)
-        out = self.model.generate(idx.to(self.device), max(new), lens=lens,
-                                  temperature=[p[2] for p in params],
-                                  top_k=[p[3] for p in params], top_p=[p[4] for p in params],
-                                  seeds=[p[5] for p in params]).cpu()
-        return [out[b, : new[b]].tolist() for b in range(len(reqs))]
+        kw = dict(lens=lens, temperature=[p[2] for p in params], top_k=[p[3] for p in params],
+                  top_p=[p[4] for p in params], seeds=[p[5] for p in params])
+        if lps is None or all(m is None for m in lps):
+            out = self.model.generate(idx.to(self.device), max(new), **kw).cpu()
+            toks = [out[b, : new[b]].tolist() for b in range(len(reqs))]
+            return toks if lps is None else [{"tokens": t} for t in toks]
+        out, lp, ids, tlp = (t.cpu() for t in self.model.generate(
+            idx.to(self.device), max(new), logprobs=max(m for m in lps if m is not None), **kw))
+        res = []
+        for b, m in enumerate(lps):
+            res.append({"tokens": out[b, : new[b]].tolist()})
+            if m is not None:
+                res[-1].update(_logprob_fields(lp[b, : new[b]].tolist(), ids[b, : new[b]].tolist(),
+                                               tlp[b, : new[b]].tolist(), m))
+        return res
 
     @batch(max_batch_size=8, batch_wait_timeout_s=0.01)
     async def _generate_batch(self, reqs):
+        from ray_amd.ops.functional import LOGPROB_MAX_TOP
+
         results = [None] * len(reqs)
-        params = {}
+        params, lps = {}, {}
         for i, r in enumerate(reqs):
             try:
+                lps[i] = _request_logprobs(r, LOGPROB_MAX_TOP)
                 params[i] = self._params(r)
             except Exception as e:  # noqa: BLE001  (one bad request must not fail its batch)
                 results[i] = {"error": f"{type(e).__name__}: {e}"}
         if any(p[2] > 0 or reqs[i].get("top_p") is not None or reqs[i].get("seed") is not None
-               for i, p in params.items()):
+               or lps[i] is not None for i, p in params.items()):
             # one call, split only where the longest prompt and the longest continuation
             # of the batch together would not fit the model's positions
             chunks, cur = [], []
@@ -138,9 +190,10 @@ class GPT2Server:
             for members in chunks:
                 try:
                     got = self._run_sampled([reqs[i] for i in members],
-                                            [params[i] for i in members])
-                    for i, toks in zip(members, got):
-                        results[i] = {"tokens": toks}
+                                            [params[i] for i in members],
+                                            [lps[i] for i in members])
+                    for i, res in zip(members, got):
+                        results[i] = res
                 except ValueError as e:
                     for i in members:
                         results[i] = {"error": f"ValueError: {e}"}
@@ -208,7 +261,8 @@ class GPT2EngineServer:
 
     def __init__(self, config="small", state_dict_path=None, seed=0, slots=None,
                  eos_token_id=None, device=None, poll_every=None, prefixes=None,
-                 prefill_chunk=None, adapters=None, lora_rank=16, speculate=0, ngram=(2, 4)):
+                 prefill_chunk=None, adapters=None, lora_rank=16, speculate=0, ngram=(2, 4),
+                 logprobs=None):
         import queue
         import threading
 
@@ -227,6 +281,7 @@ class GPT2EngineServer:
         self._aids = {}  # adapter name -> the engine's adapter slot
         self._prefill_chunk = prefill_chunk
         self._speculate, self._ngram = speculate, ngram
+        self._logprobs = logprobs  # the engine's N (None: it keeps none)
         self._pids = {}  # prefix name -> the engine's prefix id
         ready = threading.Event()
         self._thread = threading.Thread(
@@ -261,7 +316,7 @@ class GPT2EngineServer:
             eng = GPT2Engine(model.eval(), slots=slots, eos_token_id=eos_token_id,
                              prefix_slots=len(self._prefixes),
                              prefill_chunk=self._prefill_chunk, speculate=self._speculate,
-                             ngram=self._ngram, **kw)
+                             ngram=self._ngram, logprobs=self._logprobs, **kw)
             for i, (name, state) in enumerate(self._adapters.items()):
                 if not isinstance(state, dict):
                     state = torch.load(state, map_location="cpu")
@@ -302,7 +357,8 @@ class GPT2EngineServer:
                     rid = eng.submit(req["tokens"], p[1], temperature=p[2], top_k=p[3],
                                      top_p=p[4], seed=p[5],
                                      prefix=self._pids.get(req.get("prefix")),
-                                     adapter=self._aids.get(req.get("adapter")))
+                                     adapter=self._aids.get(req.get("adapter")),
+                                     logprobs=req.get("logprobs"))
                 except ValueError as e:
                     loop.call_soon_threadsafe(sink.put_nowait, ("error", f"ValueError: {e}"))
                     continue
@@ -318,12 +374,15 @@ class GPT2EngineServer:
                                               ("error", f"{type(e).__name__}: {e}"))
                 self._failure = e
                 return
-            for rid, new, finished in events:
+            for rid, new, finished, *info in events:
                 key, loop, sink = sinks[rid]
                 if finished:
                     del sinks[rid]
                     rids.pop(key, None)
-                loop.call_soon_threadsafe(sink.put_nowait, ("tokens", new, finished))
+                # (an engine with logprobs: the event's fourth field, None for a request
+                # that asked for none)
+                loop.call_soon_threadsafe(sink.put_nowait,
+                                          ("tokens", new, finished, info[0] if info else None))
 
     def close(self):
         self._inbox.put(("stop",))
@@ -331,7 +390,7 @@ class GPT2EngineServer:
 
     # ------------------------------------------------------------------ the callers' side
     async def _chunks(self, request):
-        """The request's ("tokens", new, finished) items as the engine's polls produce
+        """The request's ("tokens", new, finished, info) items as the engine's polls produce
         them, or one ("error", message); cancels the request when the consumer leaves."""
         import asyncio
 
@@ -339,6 +398,7 @@ class GPT2EngineServer:
             request = await request.json()
         try:
             p = _request_params(self.cfg, self.seed, request)
+            _request_logprobs(request, self._logprobs)
             name = request.get("prefix")
             if name is not None and (not isinstance(name, str) or name not in self._pids):
                 raise ValueError(f"unknown prefix {name!r}")
@@ -365,24 +425,39 @@ class GPT2EngineServer:
             if not finished:  # the generator was closed or the task cancelled
                 self._inbox.put(("cancel", key))
 
+    @staticmethod
+    def _fields(request, info):
+        """A chunk's logprob fields ({} for a request that asked for none)."""
+        if info is None:
+            return {}
+        return _logprob_fields(info["logprobs"], info["top_ids"], info["top_logprobs"],
+                               request["logprobs"])
+
     async def __call__(self, request):
-        toks = []
+        if not isinstance(request, dict):  # HTTP: a JSON body
+            request = await request.json()
+        res = {"tokens": []}
         async for item in self._chunks(request):
             if item[0] == "error":
                 return {"error": item[1]}
-            toks.extend(item[1])
-        return {"tokens": toks}
+            res["tokens"].extend(item[1])
+            for k, v in self._fields(request, item[3]).items():
+                res.setdefault(k, []).extend(v)
+        return res
 
     async def stream(self, request):
+        if not isinstance(request, dict):  # HTTP: a JSON body
+            request = await request.json()
         chunks = self._chunks(request)
         try:
             async for item in chunks:
                 if item[0] == "error":
                     yield {"error": item[1], "finished": True}
                 elif item[2]:
-                    yield {"tokens": item[1], "finished": True}
+                    yield {"tokens": item[1], **self._fields(request, item[3]),
+                           "finished": True}
                 else:
-                    yield {"tokens": item[1]}
+                    yield {"tokens": item[1], **self._fields(request, item[3])}
         finally:
             await chunks.aclose()
 
@@ -390,7 +465,7 @@ class GPT2EngineServer:
 def build_gpt2_app(config="small", state_dict_path=None, seed=0, max_batch_size=8,
                    batch_wait_timeout_s=0.01, device=None, continuous=False, slots=None,
                    eos_token_id=None, prefixes=None, prefill_chunk=None, adapters=None,
-                   lora_rank=16, speculate=0, ngram=(2, 4)):
+                   lora_rank=16, speculate=0, ngram=(2, 4), logprobs=None):
     """A Serve application around one ``GPT2Server`` replica (``serve.run`` it). ``config``
     names a ``GPT2Config`` preset; without ``state_dict_path`` the weights are the seeded
     random init. ``device`` None: the GPU assigned to the replica, else the CPU.
@@ -405,11 +480,14 @@ def build_gpt2_app(config="small", state_dict_path=None, seed=0, max_batch_size=
     with ``"adapter": "name"``; a ``prefixes`` value may be ``{"tokens": [...], "adapter":
     "name"}``. ``speculate=k`` (1..8; needs ``continuous=True`` too) turns on the engine's
     speculative decoding with prompt-lookup drafts of the n-gram lengths ``ngram=(lo, hi)``:
-    the same tokens, up to k + 1 of them per device step."""
+    the same tokens, up to k + 1 of them per device step. ``logprobs=N`` (0..8, with
+    ``continuous=True``): the engine keeps per-token log-probabilities and the top N
+    alternatives, and a request may ask for ``"logprobs": m`` <= N. The static server
+    needs no option and ignores this one: it answers ``"logprobs": m`` up to 8."""
     if continuous:
         dep = deployment(GPT2EngineServer, name="GPT2EngineServer")
         return dep.bind(config, state_dict_path, seed, slots, eos_token_id, device, None,
-                        prefixes, prefill_chunk, adapters, lora_rank, speculate, ngram)
+                        prefixes, prefill_chunk, adapters, lora_rank, speculate, ngram, logprobs)
     if prefixes or prefill_chunk is not None or adapters or speculate:
         raise ValueError("prefixes, prefill_chunk, adapters and speculate need continuous=True")
     dep = deployment(GPT2Server, name="GPT2Server")
