@@ -34,6 +34,10 @@ MI355X-first choices:
   (ops/csrc/attn_extend.hip): the engine's shared prompt prefixes and chunked prefill.
   ``verify_step`` runs the same layers over a window of drafted tokens per row and returns
   the logits after every one of them: the engine's speculative decoding.
+  Repetition / presence / frequency penalties, logit bias and a minimum length before EOS
+  (``generate(..., repetition_penalty=, ...)``) are edits of the logits buffer by
+  ``rf.logit_process`` (ops/csrc/logit_proc.hip) before the sampler reads it, on the device
+  and inside the captured step.
   The three inference passes (prompt, extend, decode) run ONE layer loop, ``_layers``, and
   hand it their attention step; the training ``forward`` keeps its own (autograd ops).
 """
@@ -177,7 +181,7 @@ class _SeededSampler:
     and a token then costs one replay."""
 
     def __init__(self, model, cache, logits, out, temperature, top_k, top_p, seeds, eos,
-                 adapters=None, logprobs=None):
+                 adapters=None, logprobs=None, controls=None):
         cfg = model.cfg
         dev = out.device
         B = out.shape[0]
@@ -198,6 +202,14 @@ class _SeededSampler:
             self.top_n = logprobs
             self.lp = _logprob_tables(B, out.shape[1], logprobs, dev)
             self.cols = torch.zeros(B, dtype=torch.int32, device=dev)
+        # controls=(LogitControls, ...): the logits buffer holds PROCESSED logits whenever the
+        # sampler reads it (rf.logit_process on the prefill's here, on decode_step's in _step);
+        # n_out counts the tokens in ``out``, advanced where ``col`` is (None: no such call)
+        self.ctl = None
+        if controls is not None:
+            self.ctl = controls
+            self.n_out = torch.zeros(B, dtype=torch.int32, device=dev)
+            self.ctl.process(self.logits, self.out, self.n_out, self.eos)
         self.tok = None  # the sampler's output (inside a capture: the graph's static buffer)
         self.graph = None
 
@@ -218,6 +230,9 @@ class _SeededSampler:
         if self.lp is not None:
             self.cols += 1
         self.model.decode_step(self.tok, self.cache, out=self.buf, adapters=self.adapters)
+        if self.ctl is not None:
+            self.n_out += 1  # ``out`` already holds the token just drawn
+            self.ctl.process(self.logits, self.out, self.n_out, self.eos)
 
     def draw_last(self):
         """The last token of a call needs no ``decode_step`` after it."""
@@ -245,6 +260,103 @@ def _checked_top_n(name, n):
     if isinstance(n, bool) or not isinstance(n, int) or not 0 <= n <= rf.LOGPROB_MAX_TOP:
         raise ValueError(f"{name} must be an int in 0..{rf.LOGPROB_MAX_TOP}, got {n!r}")
     return n
+
+
+def checked_controls(vocab_size, max_new_tokens, eos_token_id, repetition_penalty=None,
+                     presence_penalty=None, frequency_penalty=None, min_new_tokens=None,
+                     logit_bias=None):
+    """One request's logit-processor controls, checked: ``(repetition, presence, frequency,
+    min_new, [(id, value), ...])``, or None when none of them is given. ``ValueError`` for
+    a penalty that is not finite and > 0, a presence / frequency that is not finite, a bias
+    value that is neither finite nor ``-inf``, more than ``rf.LOGIT_BIAS_MAX`` bias entries,
+    an id outside ``[0, vocab_size)``, or ``min_new_tokens`` outside ``0..max_new_tokens``
+    (non-zero needs ``eos_token_id``)."""
+    if repetition_penalty is None and presence_penalty is None and frequency_penalty is None \
+            and min_new_tokens is None and logit_bias is None:
+        return None
+
+    def number(name, v, default):
+        if v is None:
+            return default
+        if isinstance(v, bool) or not isinstance(v, (int, float)):
+            raise ValueError(f"{name} must be a number, got {v!r}")
+        return float(v)
+
+    rp = number("repetition_penalty", repetition_penalty, 1.0)
+    if not (math.isfinite(rp) and rp > 0):
+        raise ValueError("repetition_penalty must be finite and > 0")
+    pp = number("presence_penalty", presence_penalty, 0.0)
+    fp = number("frequency_penalty", frequency_penalty, 0.0)
+    if not (math.isfinite(pp) and math.isfinite(fp)):
+        raise ValueError("presence_penalty and frequency_penalty must be finite")
+    mn = 0 if min_new_tokens is None else min_new_tokens
+    if isinstance(mn, bool) or not isinstance(mn, int) or not 0 <= mn <= max_new_tokens:
+        raise ValueError(f"min_new_tokens must be an int in 0..max_new_tokens "
+                         f"({max_new_tokens}), got {min_new_tokens!r}")
+    if mn and eos_token_id is None:
+        raise ValueError("min_new_tokens needs eos_token_id")
+    bias = []
+    if logit_bias is not None:
+        if not isinstance(logit_bias, dict):
+            raise ValueError("logit_bias must be a dict {token: value}")
+        if len(logit_bias) > rf.LOGIT_BIAS_MAX:
+            raise ValueError(f"logit_bias has {len(logit_bias)} entries, at most "
+                             f"{rf.LOGIT_BIAS_MAX} fit")
+        for t, v in logit_bias.items():
+            if isinstance(t, bool) or not isinstance(t, int) or not 0 <= t < vocab_size:
+                raise ValueError(f"logit_bias ids must be ints in [0, {vocab_size}), got {t!r}")
+            v = number("a logit_bias value", v, float("nan"))
+            if not (math.isfinite(v) or v == float("-inf")):
+                raise ValueError("logit_bias values must be finite or -inf")
+            bias.append((t, v))
+    return rp, pp, fp, mn, bias
+
+
+class LogitControls:
+    """The per-row tables of ``rf.logit_process`` for R rows, at fixed addresses: the
+    parameters (neutral until ``put``), the bias lists and the prompts int32 [R, width]."""
+
+    def __init__(self, R, width, device):
+        i32, f32 = torch.int32, torch.float32
+        self.repetition = torch.ones(R, dtype=f32, device=device)
+        self.presence = torch.zeros(R, dtype=f32, device=device)
+        self.frequency = torch.zeros(R, dtype=f32, device=device)
+        self.min_new = torch.zeros(R, dtype=i32, device=device)
+        self.bias_ids = torch.zeros(R, rf.LOGIT_BIAS_MAX, dtype=i32, device=device)
+        self.bias_vals = torch.zeros(R, rf.LOGIT_BIAS_MAX, dtype=f32, device=device)
+        self.n_bias = torch.zeros(R, dtype=i32, device=device)
+        self.prompt = torch.zeros(R, width, dtype=i32, device=device)
+        self.prompt_len = torch.zeros(R, dtype=i32, device=device)
+
+    def put(self, rows, controls, prompts):
+        """Writes rows ``rows`` (int64 [n] on the device): ``controls[i]`` a
+        ``checked_controls`` result (None: neutral), ``prompts[i]`` the row's prompt tokens.
+        Two uploads, however many rows."""
+        n, NB = len(controls), rf.LOGIT_BIAS_MAX
+        flt = torch.zeros(n, 3 + NB, dtype=torch.float32)
+        ints = torch.zeros(n, 3 + NB + self.prompt.shape[1], dtype=torch.int32)
+        for i, (c, p) in enumerate(zip(controls, prompts)):
+            rp, pp, fp, mn, bias = c if c is not None else (1.0, 0.0, 0.0, 0, [])
+            flt[i, :3] = torch.tensor([rp, pp, fp])
+            ints[i, 0], ints[i, 1], ints[i, 2] = mn, len(bias), len(p)
+            if bias:
+                ints[i, 3: 3 + len(bias)] = torch.tensor([t for t, _ in bias], dtype=torch.int32)
+                flt[i, 3: 3 + len(bias)] = torch.tensor([v for _, v in bias])
+            ints[i, 3 + NB: 3 + NB + len(p)] = torch.as_tensor(p, dtype=torch.int32)
+        flt, ints = flt.to(rows.device), ints.to(rows.device)
+        for dst, src in ((self.repetition, flt[:, 0]), (self.presence, flt[:, 1]),
+                         (self.frequency, flt[:, 2]), (self.bias_vals, flt[:, 3:]),
+                         (self.min_new, ints[:, 0]), (self.n_bias, ints[:, 1]),
+                         (self.prompt_len, ints[:, 2]), (self.bias_ids, ints[:, 3: 3 + NB]),
+                         (self.prompt, ints[:, 3 + NB:])):
+            dst.index_copy_(0, rows, src)
+
+    def process(self, logits, out, n_out, eos, **kw):
+        """``rf.logit_process`` on ``logits`` with these tables."""
+        return rf.logit_process(logits, self.prompt, self.prompt_len, out, n_out,
+                                self.repetition, self.presence, self.frequency, self.min_new,
+                                self.bias_ids, self.bias_vals, self.n_bias, eos_token_id=eos,
+                                **kw)
 
 
 def _per_row(name, value, default, B, cast):
@@ -575,7 +687,8 @@ class GPT2(nn.Module):
     @torch.no_grad()
     def generate(self, idx, max_new_tokens, *, lens=None, temperature=0.0, top_k=None,
                  top_p=None, seeds=None, eos_token_id=None, generator=None, graph=False,
-                 adapters=None, logprobs=None):
+                 adapters=None, logprobs=None, repetition_penalty=None, presence_penalty=None,
+                 frequency_penalty=None, min_new_tokens=None, logit_bias=None):
         """Autoregressive generation with a KV cache: ``idx`` [B, T] prompts, right-padded
         to a common length with true lengths ``lens`` (default: all T). Returns the new
         tokens [B, max_new_tokens] (int64). ``temperature`` 0 is greedy, otherwise samples
@@ -602,15 +715,35 @@ class GPT2(nn.Module):
         under the logits it was drawn from and the n most likely tokens there with theirs
         (``rf.token_logprobs``; the model's own distribution, whatever the sampling
         parameters). On every path; with ``seeds=`` and ``graph=True`` the call is captured
-        with the step and a token still costs one replay."""
+        with the step and a token still costs one replay.
+
+        Logit processors (each a scalar or a per-row sequence, ``logit_bias`` a dict
+        ``{token: value}`` or one per row; they need ``seeds=``): ``repetition_penalty`` (> 0;
+        a token of the prompt or the output so far has its logit divided by it when
+        positive, multiplied otherwise), ``presence_penalty`` and ``frequency_penalty``
+        (subtracted once, and once per occurrence, for a token of the output so far),
+        ``logit_bias`` (added; ``-inf`` bans a token; at most ``rf.LOGIT_BIAS_MAX`` entries)
+        and ``min_new_tokens`` (``eos_token_id`` cannot be drawn before that many tokens).
+        ``rf.logit_process`` edits the logits buffer in place before the sampler reads it,
+        on the device and inside the captured step: a row's tokens still depend on that row
+        alone and a token still costs one replay. ``logprobs=`` then reports the
+        distribution the token was drawn from, the processed logits. With none of them
+        given not one extra op runs and the results are what they were."""
         cfg = self.cfg
         B, T = idx.shape
         if logprobs is not None:
             _checked_top_n("logprobs", logprobs)
         ad = self._adapter_tensor(adapters, B, idx.device)
+        named = {k: v for k, v in (("repetition_penalty", repetition_penalty),
+                                   ("presence_penalty", presence_penalty),
+                                   ("frequency_penalty", frequency_penalty),
+                                   ("min_new_tokens", min_new_tokens),
+                                   ("logit_bias", logit_bias)) if v is not None}
         if seeds is None:
             if top_p is not None:
                 raise ValueError("top_p needs the device sampler: pass seeds=")
+            for k in named:
+                raise ValueError(f"{k} needs the device sampler: pass seeds=")
             if any(isinstance(v, (list, tuple, torch.Tensor)) for v in (temperature, top_k)):
                 raise ValueError("per-row temperature / top_k need the device sampler: pass "
                                  "seeds=")
@@ -643,6 +776,17 @@ class GPT2(nn.Module):
         if graph and not idx.is_cuda:
             raise ValueError("graph=True needs the model and prompts on the GPU")
         dev = idx.device
+        ctl = None
+        if named:
+            cols = {k: _per_row(k, v, None, B, lambda x: x) if k != "logit_bias" or
+                    not isinstance(v, dict) else [v] * B for k, v in named.items()}
+            rows_c = [checked_controls(cfg.vocab_size, max_new_tokens, eos_token_id,
+                                       **{k: col[b] for k, col in cols.items()})
+                      for b in range(B)]
+            ctl = LogitControls(B, T, dev)
+            idx_l = idx.tolist()
+            ctl.put(torch.arange(B, device=dev), rows_c,
+                    [idx_l[b][: lens_l[b]] for b in range(B)])
         cache = KVCache(cfg, B, max(lens_l) + max_new_tokens, dev, self.wte.dtype)
         logits = self.prefill(idx, torch.tensor(lens_l, dtype=torch.int32, device=dev), cache,
                               adapters=ad)
@@ -650,7 +794,7 @@ class GPT2(nn.Module):
         if seeds is not None:
             eos = None if eos_token_id is None else int(eos_token_id)
             step = _SeededSampler(self, cache, logits, out, temps, ks, ps, seeds_l, eos, ad,
-                                  logprobs)
+                                  logprobs, ctl)
             res = out if logprobs is None else (out,) + step.lp
             if max_new_tokens > 1:
                 step()

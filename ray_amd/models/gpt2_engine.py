@@ -90,6 +90,25 @@ them; a poll is still one download. A request's entries are those of ``generate(
 seeds=[seed], logprobs=m)`` on it alone, cut after the first EOS, with prefixes, chunked
 prefill, adapters, ``cancel`` and every ``speculate``.
 
+Logit processors (``logit_processors=True``; False, the default, is the engine without them:
+no buffer, no extra op, and ``submit`` rejects the fields): ``submit(..., repetition_penalty=,
+presence_penalty=, frequency_penalty=, logit_bias=, min_new_tokens=)`` as in ``generate``. The
+per-slot parameters, the bias lists and the prompts (``LogitControls``: int32 [S, max_len]
+with their lengths, the prefix's tokens included) sit at fixed addresses and are written
+when a slot's prompt is complete; ``rf.logit_process`` then edits that round's prefill logits
+rows, ``rows`` naming their slots, before they go into ``self.buf``. The invariant: ``self.buf``
+holds PROCESSED rows. The plain step keeps it with one more call at its end, after
+``decode_step``, on ``self.logits`` with ``out``, ``n_out`` and ``active`` as ``slot_advance``
+left them. The speculative step makes one call on the window's logits between
+``verify_step`` and the window's sampler, with ``rows = slot``, ``extra = win[slot]`` and
+``n_extra = j + 1`` for window row j (active iff ``j < n_win`` and the slot is): row j sees
+exactly the tokens that precede its position, so the row ``rf.spec_accept`` copies into
+``self.buf`` is already processed with every kept token and is not processed again. A
+request's tokens and logprobs (those of the processed logits, the distribution the token
+was drawn from) are those of ``generate(..., seeds=[seed], <same controls>)`` on it alone,
+cut after the first EOS, with prefixes, chunked prefill, adapters, ``cancel``, every
+``speculate`` and ``logprobs``; a request that names no control is untouched.
+
 Single-threaded by contract: every call comes from one thread."""
 
 from __future__ import annotations
@@ -100,29 +119,30 @@ import math
 import numpy as np
 import torch
 
-from ray_amd.models.gpt2 import GPT2, KVCache
+from ray_amd.models.gpt2 import GPT2, KVCache, LogitControls, checked_controls
 from ray_amd.ops import functional as rf
 from ray_amd.ops.graph_lock import CapturedStep
 
 
 class _Request:
     __slots__ = ("rid", "tokens", "max_new", "temperature", "top_k", "top_p", "seed", "pid",
-                 "adapter", "logprobs")
+                 "adapter", "logprobs", "controls")
 
     def __init__(self, rid, tokens, max_new, temperature, top_k, top_p, seed, pid=None,
-                 adapter=-1, logprobs=None):
+                 adapter=-1, logprobs=None, controls=None):
         # tokens: the whole prompt (the prefix's tokens included); pid: the prefix it names
         self.rid, self.tokens, self.max_new = rid, tokens, max_new
         self.temperature, self.top_k, self.top_p, self.seed = temperature, top_k, top_p, seed
         self.pid = pid
         self.adapter = adapter  # -1: the base model
         self.logprobs = logprobs  # None: the request reports none; else its top-n width
+        self.controls = controls  # a checked_controls result (None: neutral)
 
 
 class GPT2Engine:
     def __init__(self, model: GPT2, slots=8, max_len=None, eos_token_id=None, graph=None,
                  poll_every=8, prefix_slots=0, prefill_chunk=None, lora=None, speculate=0,
-                 ngram=(2, 4), drafter=None, logprobs=None):
+                 ngram=(2, 4), drafter=None, logprobs=None, logit_processors=False):
         cfg = model.cfg
         dev = model.wte.device
         S = int(slots)
@@ -213,6 +233,16 @@ class GPT2Engine:
                 self._win_idx = torch.arange(speculate + 1, dtype=torch.int32,
                                              device=dev).unsqueeze(0)
 
+        self.ctl = None
+        if logit_processors:
+            self.ctl = LogitControls(S, self.max_len, dev)
+            if speculate:
+                W = speculate + 1
+                self._ctl_rows = self.cache.rows.repeat_interleave(W)
+                self._ctl_idx = torch.arange(W, dtype=torch.int32, device=dev).unsqueeze(0)
+                self._ctl_n_extra = torch.arange(1, W + 1, dtype=torch.int32,
+                                                 device=dev).repeat(S)
+
         self._queue = collections.deque()
         self._slot_req = [None] * S  # the request running in each slot
         self._seen_host = [0] * S
@@ -247,6 +277,9 @@ class GPT2Engine:
         rf.slot_advance(tok, self.cache.lens, self.n_out, self.max_new, self.active, self.out,
                         self.eos)
         self.model.decode_step(tok, self.cache, out=self.buf, adapters=self.adapter)
+        if self.ctl is not None:
+            # out / n_out hold tok, and a slot that just finished is inactive
+            self.ctl.process(self.logits, self.out, self.n_out, self.eos, active=self.active)
 
     def _ngram_drafter(self, tok0, hist, lens, n_out, max_new, active):
         return rf.spec_draft(tok0, hist, lens, n_out, max_new, active, self.speculate,
@@ -261,6 +294,14 @@ class GPT2Engine:
         win, n_win = self._drafter(tok0, self.hist, lens, self.n_out, self.max_new, self.active)
         self.model.verify_step(win, n_win, self.cache, out=self.logits_win,
                                adapters=self.adapter)
+        if self.ctl is not None:
+            # window row j: the logits after win[s, :j + 1], which follow out[s, :n_out]
+            live = (self._ctl_idx < n_win.unsqueeze(1)) & self.active.bool().unsqueeze(1)
+            self.ctl.process(self.logits_win.view(S * W, -1)[:, :V], self.out, self.n_out,
+                             self.eos, rows=self._ctl_rows,
+                             extra=win.unsqueeze(1).expand(S, W, W).reshape(S * W, W),
+                             n_extra=self._ctl_n_extra,
+                             active=live.to(torch.uint8).view(S * W))
         temperature, top_k, top_p, seeds = (t.view(S * W) for t in self._win_params)
         # window row i holds the logits at position lens + 1 + i
         cand = rf.sample_logits(self.logits_win.view(S * W, -1)[:, :V], temperature, top_k, top_p,
@@ -382,7 +423,9 @@ class GPT2Engine:
         self._prefix_free.append(self._prefixes.pop(pid)[0])
 
     def submit(self, tokens, max_new_tokens, temperature=0.0, top_k=None, top_p=None, seed=0,
-               prefix=None, adapter=None, logprobs=None):
+               prefix=None, adapter=None, logprobs=None, repetition_penalty=None,
+               presence_penalty=None, frequency_penalty=None, logit_bias=None,
+               min_new_tokens=None):
         """Queues a request and returns its id; a bad request raises ``ValueError`` and
         queues nothing. ``prefix``: an ``add_prefix`` id; ``tokens`` is then the non-empty
         continuation and the request's prompt is the prefix's tokens followed by it.
@@ -390,8 +433,18 @@ class GPT2Engine:
         or the prefix's adapter when ``prefix`` is given; another adapter than the prefix's
         is an error). ``logprobs``: an int in 0..N on an engine built with ``logprobs=N``:
         the request's events carry the log-probability of every token and the ``logprobs``
-        most likely tokens at its position (None: they carry none)."""
+        most likely tokens at its position (None: they carry none). ``repetition_penalty``,
+        ``presence_penalty``, ``frequency_penalty``, ``logit_bias`` and ``min_new_tokens``: as
+        in ``generate``, on an engine built with ``logit_processors=True``."""
         tokens = self._checked_tokens(tokens, "request")
+        controls = {"repetition_penalty": repetition_penalty,
+                    "presence_penalty": presence_penalty,
+                    "frequency_penalty": frequency_penalty, "logit_bias": logit_bias,
+                    "min_new_tokens": min_new_tokens}
+        for k, v in controls.items():
+            if v is not None and self.ctl is None:
+                raise ValueError(f"{k} given, but the engine has no logit processors: "
+                                 "logit_processors=True")
         if logprobs is not None:
             if self.logprobs is None:
                 raise ValueError("logprobs given, but the engine keeps none: logprobs=")
@@ -428,10 +481,11 @@ class GPT2Engine:
         if seed >= 2 ** 63:
             seed -= 2 ** 64
         top_k = max(0, min(top_k, 2 ** 31 - 1))
+        controls = checked_controls(self.model.cfg.vocab_size, max_new, self.eos, **controls)
         rid = self._next_rid
         self._next_rid += 1
         self._queue.append(_Request(rid, tokens, max_new, temperature, top_k, top_p, seed,
-                                    prefix, adapter, logprobs))
+                                    prefix, adapter, logprobs, controls))
         return rid
 
     def cancel(self, rid):
@@ -535,6 +589,12 @@ class GPT2Engine:
             sel = torch.tensor(done).to(dev)
             ints, flts, logits = ints[sel], flts[sel], logits[sel]
             sl = ints[:, 0]
+        self.n_out.index_fill_(0, sl, 0)
+        if self.ctl is not None:
+            # the slots' tables (the whole prompt, the prefix's tokens included), then this
+            # round's rows: self.buf only ever holds processed logits
+            self.ctl.put(sl, [reqs[j].controls for j in done], [reqs[j].tokens for j in done])
+            self.ctl.process(logits, self.out, self.n_out, self.eos, rows=sl.to(torch.int32))
         self.logits.index_copy_(0, sl, logits)
         self.top_k.index_copy_(0, sl, ints[:, 2].to(torch.int32))
         self.max_new.index_copy_(0, sl, ints[:, 3].to(torch.int32))
@@ -543,7 +603,6 @@ class GPT2Engine:
             self.adapter.index_copy_(0, sl, ints[:, 6].to(torch.int32))
         self.temperature.index_copy_(0, sl, flts[:, 0])
         self.top_p.index_copy_(0, sl, flts[:, 1])
-        self.n_out.index_fill_(0, sl, 0)
         self._seen.index_fill_(0, sl, 0)
         if self.speculate:
             # the whole prompt by position, for the drafter: one more upload per round

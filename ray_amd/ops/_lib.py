@@ -136,6 +136,9 @@ _SIGS = {
                                                                 c_void_p],
     "ra_token_logprobs_max_top": [],
     "ra_token_logprobs": [c_void_p, c_long] + [c_void_p] * 7 + [c_int] * 5 + [c_void_p],
+    "ra_logit_process_max_bias": [],
+    "ra_logit_process_max_context": [],
+    "ra_logit_process": [c_void_p, c_long] + [c_void_p] * 15 + [c_int] * 8 + [c_void_p],
     "ra_gemm_nt": [c_void_p, c_long, c_void_p, c_long, c_void_p, c_long, c_int, c_int, c_int,
                    c_int, c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_int, c_int,
                    c_void_p],

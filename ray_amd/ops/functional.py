@@ -1164,6 +1164,112 @@ def token_logprobs(logits, tok, top_n=0, vocab_size=None, out=None, rows=None, c
     return res
 
 
+LOGIT_BIAS_MAX = 64             # ops/csrc/logit_proc.hip kMaxBias (checked against the library)
+LOGIT_PROCESS_MAX_CONTEXT = 4096  # kMaxContext there: P + cap + W + NB + 1 of the HIP path
+
+
+def _table(name, op, t, shape, like, dtype):
+    if not isinstance(t, torch.Tensor) or tuple(t.shape) != tuple(shape) or t.dtype != dtype or \
+            t.device != like.device:
+        raise ValueError(f"{op}: {name} must be a {dtype} tensor {list(shape)} on {like.device}")
+
+
+def logit_process(logits, prompt, prompt_len, out, n_out, repetition, presence, frequency,
+                  min_new, bias_ids, bias_vals, n_bias, rows=None, extra=None, n_extra=None,
+                  active=None, eos_token_id=None, vocab_size=None):
+    """Repetition / presence / frequency penalties, logit bias and the minimum length before
+    EOS, applied IN PLACE to the rows of ``logits`` [B, Vs] (the first ``vocab_size or Vs``
+    columns count) as a function of each row's own token history. Semantics:
+    ``reference.logit_process``, bit for bit. Returns ``logits``.
+
+    The context of logits row b is row ``rows[b]`` (int32 [B], default b) of ``prompt`` int32
+    [R, P] / ``prompt_len`` int32 [R], ``out`` int64 [R, cap] / ``n_out`` int32 [R] and of the
+    parameters ``repetition``, ``presence``, ``frequency`` fp32 [R], ``min_new`` int32 [R],
+    ``bias_ids`` int32 [R, NB], ``bias_vals`` fp32 [R, NB] (NB <= ``LOGIT_BIAS_MAX``),
+    ``n_bias`` int32 [R]. ``extra`` int64 [B, W] with ``n_extra`` int32 [B]: per logits row,
+    the tokens that follow ``out[r, :n_out[r]]``. ``active`` uint8 [B]. A row with
+    ``active[b] == 0``, a context row or a length out of range, or neutral parameters keeps
+    its bytes; so does every element that no rule names.
+
+    HIP kernel (ops/csrc/logit_proc.hip: one launch, one workgroup per row, every index read
+    and checked on the device, no host sync, capturable; it touches the named elements only)
+    for GPU tensors with bf16 logits of unit column stride, at most ``SAMPLE_MAX_VOCAB``
+    columns and ``P + cap + W + NB + 1 <= LOGIT_PROCESS_MAX_CONTEXT``; the rows may be a
+    column slice of a wider buffer, edited in place. CPU tensors, other dtypes, wider
+    vocabularies and longer contexts use the plain-torch reference."""
+    op = "logit_process"
+    if not isinstance(logits, torch.Tensor) or logits.dim() != 2:
+        raise ValueError(f"{op}: logits must be [B, V]")
+    B, Vs = logits.shape
+    V = Vs if vocab_size is None else int(vocab_size)
+    if B < 1 or V < 1 or V > Vs:
+        raise ValueError(f"{op}: vocab_size {V} does not fit logits {tuple(logits.shape)}")
+    if logits.dtype not in ref._BITS:
+        raise ValueError(f"{op}: logits must be floating point")
+    if not isinstance(prompt, torch.Tensor) or prompt.dim() != 2 or prompt.shape[0] < 1:
+        raise ValueError(f"{op}: prompt must be an int32 tensor [R, P]")
+    R, P = prompt.shape
+    _table("prompt", op, prompt, (R, P), logits, torch.int32)
+    if not isinstance(out, torch.Tensor) or out.dim() != 2:
+        raise ValueError(f"{op}: out must be an int64 tensor [R, cap]")
+    cap = out.shape[1]
+    _table("out", op, out, (R, cap), logits, torch.int64)
+    if not isinstance(bias_ids, torch.Tensor) or bias_ids.dim() != 2 or \
+            bias_ids.shape[1] > LOGIT_BIAS_MAX:
+        raise ValueError(f"{op}: bias_ids must be an int32 tensor [R, NB], NB <= "
+                         f"{LOGIT_BIAS_MAX}")
+    NB = bias_ids.shape[1]
+    _table("bias_ids", op, bias_ids, (R, NB), logits, torch.int32)
+    _table("bias_vals", op, bias_vals, (R, NB), logits, torch.float32)
+    for name, t, dt in (("prompt_len", prompt_len, torch.int32), ("n_out", n_out, torch.int32),
+                        ("repetition", repetition, torch.float32),
+                        ("presence", presence, torch.float32),
+                        ("frequency", frequency, torch.float32),
+                        ("min_new", min_new, torch.int32), ("n_bias", n_bias, torch.int32)):
+        _int_vec(name, op, t, R, logits, dt)
+    if rows is None:
+        if R < B:
+            raise ValueError(f"{op}: {B} logits rows need rows= to share {R} context rows")
+    else:
+        _int_vec("rows", op, rows, B, logits)
+    W = 0
+    if (extra is None) != (n_extra is None):
+        raise ValueError(f"{op}: extra and n_extra go together")
+    if extra is not None:
+        if not isinstance(extra, torch.Tensor) or extra.dim() != 2:
+            raise ValueError(f"{op}: extra must be an int64 tensor [B, W]")
+        W = extra.shape[1]
+        _table("extra", op, extra, (B, W), logits, torch.int64)
+        _int_vec("n_extra", op, n_extra, B, logits)
+    if active is not None:
+        _int_vec("active", op, active, B, logits, torch.uint8)
+    eos = -1
+    if eos_token_id is not None:
+        if isinstance(eos_token_id, bool) or not isinstance(eos_token_id, int):
+            raise ValueError(f"{op}: eos_token_id must be an int or None")
+        if 0 <= eos_token_id < V:
+            eos = eos_token_id
+    hip = _hip(logits) and logits.dtype == torch.bfloat16 and V <= SAMPLE_MAX_VOCAB and \
+        logits.stride(1) == 1 and (B == 1 or logits.stride(0) >= V) and \
+        P + cap + W + NB + 1 <= LOGIT_PROCESS_MAX_CONTEXT and (extra is None or W > 0)
+    if not hip:
+        return ref.logit_process(logits, prompt, prompt_len, out, n_out, repetition, presence,
+                                 frequency, min_new, bias_ids, bias_vals, n_bias, rows, extra,
+                                 n_extra, active, None if eos < 0 else eos, V)
+    L = _lib.lib()
+    assert L.ra_logit_process_max_bias() == LOGIT_BIAS_MAX
+    assert L.ra_logit_process_max_context() == LOGIT_PROCESS_MAX_CONTEXT
+    c = torch.Tensor.contiguous
+    check(L.ra_logit_process(
+        ptr(logits), max(logits.stride(0), V), ptr(None if rows is None else c(rows)),
+        ptr(None if active is None else c(active)), ptr(c(prompt)), ptr(c(prompt_len)),
+        ptr(c(out)), ptr(c(n_out)), ptr(None if extra is None else c(extra)),
+        ptr(None if extra is None else c(n_extra)), ptr(c(repetition)), ptr(c(presence)),
+        ptr(c(frequency)), ptr(c(min_new)), ptr(c(bias_ids)), ptr(c(bias_vals)), ptr(c(n_bias)),
+        B, V, R, P, cap, W, NB, eos, stream_ptr()), op)
+    return logits
+
+
 # --------------------------------------------------------------------- cross entropy
 class _CrossEntropy(torch.autograd.Function):
     @staticmethod

@@ -493,6 +493,109 @@ def token_logprobs(logits, tok, top_n=0, vocab_size=None, out=None, rows=None, c
     return out
 
 
+_BITS = {torch.bfloat16: (torch.int16, 0x7FC0), torch.float16: (torch.int16, 0x7E00),
+         torch.float32: (torch.int32, 0x7FC00000), torch.float64: (torch.int64, 0x7FF8 << 48)}
+
+
+def logit_process(logits, prompt, prompt_len, out, n_out, repetition, presence, frequency,
+                  min_new, bias_ids, bias_vals, n_bias, rows=None, extra=None, n_extra=None,
+                  active=None, eos_token_id=None, vocab_size=None):
+    """Logit processors (ops/csrc/logit_proc.hip semantics): the single definition. Edits
+    ``logits`` IN PLACE and returns it. No host sync.
+
+    ``logits`` [B, Vs], of which the first ``V = vocab_size or Vs`` columns count. The context
+    of logits row b is row ``r = rows[b]`` (int32 [B], default b) of ``prompt`` int32 [R, P]
+    with ``prompt_len`` int32 [R], ``out`` int64 [R, cap] with ``n_out`` int32 [R], and the
+    parameters ``repetition``, ``presence``, ``frequency`` fp32 [R], ``min_new`` int32 [R],
+    ``bias_ids`` int32 [R, NB], ``bias_vals`` fp32 [R, NB], ``n_bias`` int32 [R]; plus, per
+    logits row, ``extra`` int64 [B, W] with ``n_extra`` int32 [B], the tokens that follow
+    ``out[r, :n_out[r]]`` for this row (a speculative window up to the row's position).
+
+    A row is skipped, its bytes kept, when ``active[b] == 0``, ``rows[b]`` is outside
+    ``[0, R)``, a length is negative or exceeds its table, or its parameters are all neutral
+    (``repetition == 1``, ``presence == frequency == 0``, ``n_bias == 0``, ``min_new == 0``).
+    Otherwise *generated* is ``out[r, :n_out[r]]`` then ``extra[b, :n_extra[b]]``, *seen* is
+    ``prompt[r, :prompt_len[r]]`` with *generated*, and c(v) counts v in *generated*; ids
+    outside ``[0, V)`` in any table are ignored. Every token v that is in *seen*, is a bias
+    id, or is ``eos_token_id`` while ``len(generated) < min_new[r]`` is edited exactly once,
+    from ``x = float32(logits[b, v])``, every step rounded to fp32 on its own:
+
+    1. v in *seen*: ``x = x / repetition`` if ``x > 0`` else ``x * repetition``.
+    2. c(v) > 0: ``x = x - frequency * float32(c(v))``, then ``x = x - presence``.
+    3. v a bias id: ``x = x + bias_vals[r, i]``, i the lowest index holding v.
+    4. v is the banned EOS: ``x = -inf``.
+    5. x is stored rounded once to the logits' dtype (nearest even); a NaN result is stored
+       as the dtype's canonical quiet NaN (0x7FC0 for bf16).
+
+    Every other element keeps its exact bytes, the columns at and beyond V included."""
+    B, Vs = logits.shape
+    V = Vs if vocab_size is None else int(vocab_size)
+    dev = logits.device
+    R, P = prompt.shape
+    cap, NB = out.shape[1], bias_ids.shape[1]
+    r = torch.arange(B, device=dev) if rows is None else rows.long()
+    ok = (r >= 0) & (r < R)
+    if active is not None:
+        ok = ok & active.bool()
+    rc = r.clamp(0, R - 1)
+    pl, no, nb = prompt_len[rc].long(), n_out[rc].long(), n_bias[rc].long()
+    ok = ok & (pl >= 0) & (pl <= P) & (no >= 0) & (no <= cap) & (nb >= 0) & (nb <= NB)
+    gen = [(out[rc], no, cap)]
+    n_gen = no
+    if extra is not None:
+        W = extra.shape[1]
+        ne = n_extra.long()
+        ok = ok & (ne >= 0) & (ne <= W)
+        gen.append((extra.long(), ne, W))
+        n_gen = no + ne
+    rp, pp, fp = (t[rc].float().unsqueeze(1) for t in (repetition, presence, frequency))
+    mn = min_new[rc].long()
+    neutral = (rp == 1).squeeze(1) & (pp == 0).squeeze(1) & (fp == 0).squeeze(1) & (nb == 0) & \
+        (mn == 0)
+    ok = ok & ~neutral
+
+    def cols(ids, n, width):
+        # the ids that count as column indices, the others in the spare column V
+        ids = ids.long()
+        live = (torch.arange(width, device=dev).unsqueeze(0) < n.unsqueeze(1)) & (ids >= 0) & \
+            (ids < V)
+        return torch.where(live, ids, V)
+
+    one = torch.ones(1, dtype=torch.int32, device=dev)
+    in_prompt = torch.zeros(B, V + 1, dtype=torch.int32, device=dev)
+    in_prompt.scatter_(1, cols(prompt[rc], pl, P), one.expand(B, P))
+    cnt = torch.zeros(B, V + 1, dtype=torch.int32, device=dev)
+    for ids, n, width in gen:
+        cnt.scatter_add_(1, cols(ids, n, width), one.expand(B, width))
+    in_prompt, cnt = in_prompt[:, :V].bool(), cnt[:, :V]
+    gen_seen = cnt > 0
+    seen = in_prompt | gen_seen
+    named = seen
+    view = logits[:, :V]
+    x = view.float()
+    x = torch.where(seen, torch.where(x > 0, x / rp, x * rp), x)
+    x = torch.where(gen_seen, (x - fp * cnt.float()) - pp, x)
+    if NB:
+        first = torch.full((B, V + 1), NB, dtype=torch.int64, device=dev)
+        first.scatter_reduce_(1, cols(bias_ids[rc], nb, NB),
+                              torch.arange(NB, device=dev).expand(B, NB), "amin")
+        first = first[:, :V]
+        biased = first < NB
+        x = torch.where(biased, x + bias_vals[rc].float().gather(1, first.clamp(max=NB - 1)), x)
+        named = named | biased
+    if eos_token_id is not None and 0 <= int(eos_token_id) < V:
+        ban = torch.zeros(B, V, dtype=torch.bool, device=dev)
+        ban[:, int(eos_token_id)] = n_gen < mn
+        x = torch.where(ban, torch.full_like(x, float("-inf")), x)
+        named = named | ban
+    idt, nan = _BITS[logits.dtype]
+    bits = torch.where(x.isnan(), torch.full((), nan, dtype=idt, device=dev),
+                       x.to(logits.dtype).view(idt))
+    raw = view.view(idt)
+    raw.copy_(torch.where(named & ok.unsqueeze(1), bits, raw))
+    return logits
+
+
 def _f(x):
     return x.to(torch.promote_types(x.dtype, torch.float32))
 

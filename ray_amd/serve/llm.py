@@ -44,7 +44,19 @@ slice for its tokens, and a non-finite value is ``None`` (JSON has no ``-inf``).
 server routes such a batch through the device sampler, one ``generate(..., logprobs=max m)``
 call, each result cut to its own m. The continuous server needs ``build_gpt2_app(...,
 logprobs=N)``, which passes N to the engine; m above N, or m on an app built without it, is
-that request's error. A request without the field gets the response it always got."""
+that request's error. A request without the field gets the response it always got.
+
+Logit processors: a request may carry ``"repetition_penalty"``, ``"presence_penalty"``,
+``"frequency_penalty"``, ``"min_new_tokens"`` and ``"logit_bias"`` (a JSON object whose keys
+are token ids, as strings or ints; ``-inf`` values arrive as the float), with the meaning
+they have in ``GPT2.generate``. Each request is checked on its own and an error is that
+request's. The static server routes a batch that contains any of them through the device
+sampler, one ``generate`` call with every control per row (it has no ``eos_token_id``, so a
+non-zero ``min_new_tokens`` is an error there). The continuous server needs
+``build_gpt2_app(..., continuous=True, logit_processors=True)``, which passes the flag to the
+engine; without it a request that names one of the fields gets an error. With
+``"logprobs"`` the values describe the processed logits, the distribution the token was
+drawn from."""
 
 from __future__ import annotations
 
@@ -81,6 +93,36 @@ def _request_logprobs(r, limit, hint=""):
     if m > limit:
         raise ValueError(f"logprobs ({m}) exceeds the server's {limit}{hint}")
     return m
+
+
+CONTROL_FIELDS = ("repetition_penalty", "presence_penalty", "frequency_penalty",
+                  "min_new_tokens", "logit_bias")
+
+
+def _request_controls(cfg, r, new, eos, enabled=True):
+    """The request's logit-processor fields as ``generate`` / ``submit`` keyword arguments,
+    checked (``{}``: it names none). ``logit_bias`` keys may be strings."""
+    from ray_amd.models.gpt2 import checked_controls
+
+    kw = {k: r[k] for k in CONTROL_FIELDS if r.get(k) is not None}
+    if not kw:
+        return {}
+    if not enabled:
+        raise ValueError(f"{sorted(kw)[0]!r} needs build_gpt2_app(continuous=True, "
+                         "logit_processors=True)")
+    bias = kw.get("logit_bias")
+    if bias is not None:
+        if not isinstance(bias, dict):
+            raise ValueError("logit_bias must be an object {token id: value}")
+        try:
+            kw["logit_bias"] = {t if isinstance(t, int) else int(str(t), 10): v
+                                for t, v in bias.items()}
+        except ValueError:
+            raise ValueError("logit_bias keys must be token ids") from None
+        if len(kw["logit_bias"]) != len(bias):
+            raise ValueError("logit_bias names a token id twice")
+    checked_controls(cfg.vocab_size, new, eos, **kw)
+    return kw
 
 
 def _finite(v):
@@ -136,10 +178,11 @@ class GPT2Server:
                              "continuous=True, adapters=...)")
         return _request_params(self.model.cfg, self.seed, r)
 
-    def _run_sampled(self, reqs, params, lps=None):
+    def _run_sampled(self, reqs, params, lps=None, ctls=None):
         """One ragged generate call through the device sampler, every parameter per row.
         ``lps`` (each request's ``logprobs`` or None; not all None): the call reports the
-        batch's widest and every result is a dict cut to its own."""
+        batch's widest and every result is a dict cut to its own. ``ctls``: each request's
+        ``_request_controls``."""
         lens = [p[0] for p in params]
         new = [p[1] for p in params]
         idx = torch.zeros(len(reqs), max(lens), dtype=torch.long)
@@ -147,6 +190,11 @@ class GPT2Server:
             idx[b, : lens[b]] = torch.tensor(r["tokens"], dtype=torch.long)
         kw = dict(lens=lens, temperature=[p[2] for p in params], top_k=[p[3] for p in params],
                   top_p=[p[4] for p in params], seeds=[p[5] for p in params])
+        if ctls is not None and any(ctls):
+            # min_new_tokens is checked against the request's own max_new_tokens, above
+            for k in CONTROL_FIELDS:
+                if any(k in c for c in ctls):
+                    kw[k] = [c.get(k) for c in ctls]
         if lps is None or all(m is None for m in lps):
             out = self.model.generate(idx.to(self.device), max(new), **kw).cpu()
             toks = [out[b, : new[b]].tolist() for b in range(len(reqs))]
@@ -166,15 +214,17 @@ class GPT2Server:
         from ray_amd.ops.functional import LOGPROB_MAX_TOP
 
         results = [None] * len(reqs)
-        params, lps = {}, {}
+        params, lps, ctls = {}, {}, {}
         for i, r in enumerate(reqs):
             try:
                 lps[i] = _request_logprobs(r, LOGPROB_MAX_TOP)
-                params[i] = self._params(r)
+                p = self._params(r)
+                ctls[i] = _request_controls(self.model.cfg, r, p[1], None)
+                params[i] = p
             except Exception as e:  # noqa: BLE001  (one bad request must not fail its batch)
                 results[i] = {"error": f"{type(e).__name__}: {e}"}
         if any(p[2] > 0 or reqs[i].get("top_p") is not None or reqs[i].get("seed") is not None
-               or lps[i] is not None for i, p in params.items()):
+               or lps[i] is not None or ctls[i] for i, p in params.items()):
             # one call, split only where the longest prompt and the longest continuation
             # of the batch together would not fit the model's positions
             chunks, cur = [], []
@@ -191,7 +241,8 @@ class GPT2Server:
                 try:
                     got = self._run_sampled([reqs[i] for i in members],
                                             [params[i] for i in members],
-                                            [lps[i] for i in members])
+                                            [lps[i] for i in members],
+                                            [ctls[i] for i in members])
                     for i, res in zip(members, got):
                         results[i] = res
                 except ValueError as e:
@@ -262,7 +313,7 @@ class GPT2EngineServer:
     def __init__(self, config="small", state_dict_path=None, seed=0, slots=None,
                  eos_token_id=None, device=None, poll_every=None, prefixes=None,
                  prefill_chunk=None, adapters=None, lora_rank=16, speculate=0, ngram=(2, 4),
-                 logprobs=None):
+                 logprobs=None, logit_processors=False):
         import queue
         import threading
 
@@ -282,6 +333,8 @@ class GPT2EngineServer:
         self._prefill_chunk = prefill_chunk
         self._speculate, self._ngram = speculate, ngram
         self._logprobs = logprobs  # the engine's N (None: it keeps none)
+        self._logit_processors = bool(logit_processors)
+        self._eos = eos_token_id
         self._pids = {}  # prefix name -> the engine's prefix id
         ready = threading.Event()
         self._thread = threading.Thread(
@@ -316,7 +369,8 @@ class GPT2EngineServer:
             eng = GPT2Engine(model.eval(), slots=slots, eos_token_id=eos_token_id,
                              prefix_slots=len(self._prefixes),
                              prefill_chunk=self._prefill_chunk, speculate=self._speculate,
-                             ngram=self._ngram, logprobs=self._logprobs, **kw)
+                             ngram=self._ngram, logprobs=self._logprobs,
+                             logit_processors=self._logit_processors, **kw)
             for i, (name, state) in enumerate(self._adapters.items()):
                 if not isinstance(state, dict):
                     state = torch.load(state, map_location="cpu")
@@ -352,13 +406,13 @@ class GPT2EngineServer:
                         eng.cancel(rid)
                         sinks.pop(rid, None)
                     continue
-                _, key, req, p, loop, sink = msg
+                _, key, req, p, ctl, loop, sink = msg
                 try:
                     rid = eng.submit(req["tokens"], p[1], temperature=p[2], top_k=p[3],
                                      top_p=p[4], seed=p[5],
                                      prefix=self._pids.get(req.get("prefix")),
                                      adapter=self._aids.get(req.get("adapter")),
-                                     logprobs=req.get("logprobs"))
+                                     logprobs=req.get("logprobs"), **ctl)
                 except ValueError as e:
                     loop.call_soon_threadsafe(sink.put_nowait, ("error", f"ValueError: {e}"))
                     continue
@@ -399,6 +453,7 @@ class GPT2EngineServer:
         try:
             p = _request_params(self.cfg, self.seed, request)
             _request_logprobs(request, self._logprobs)
+            ctl = _request_controls(self.cfg, request, p[1], self._eos, self._logit_processors)
             name = request.get("prefix")
             if name is not None and (not isinstance(name, str) or name not in self._pids):
                 raise ValueError(f"unknown prefix {name!r}")
@@ -414,7 +469,7 @@ class GPT2EngineServer:
         key = self._next_key
         self._next_key += 1
         sink = asyncio.Queue()
-        self._inbox.put(("submit", key, request, p, asyncio.get_running_loop(), sink))
+        self._inbox.put(("submit", key, request, p, ctl, asyncio.get_running_loop(), sink))
         finished = False
         try:
             while not finished:
@@ -465,7 +520,8 @@ class GPT2EngineServer:
 def build_gpt2_app(config="small", state_dict_path=None, seed=0, max_batch_size=8,
                    batch_wait_timeout_s=0.01, device=None, continuous=False, slots=None,
                    eos_token_id=None, prefixes=None, prefill_chunk=None, adapters=None,
-                   lora_rank=16, speculate=0, ngram=(2, 4), logprobs=None):
+                   lora_rank=16, speculate=0, ngram=(2, 4), logprobs=None,
+                   logit_processors=False):
     """A Serve application around one ``GPT2Server`` replica (``serve.run`` it). ``config``
     names a ``GPT2Config`` preset; without ``state_dict_path`` the weights are the seeded
     random init. ``device`` None: the GPU assigned to the replica, else the CPU.
@@ -483,11 +539,15 @@ def build_gpt2_app(config="small", state_dict_path=None, seed=0, max_batch_size=
     the same tokens, up to k + 1 of them per device step. ``logprobs=N`` (0..8, with
     ``continuous=True``): the engine keeps per-token log-probabilities and the top N
     alternatives, and a request may ask for ``"logprobs": m`` <= N. The static server
-    needs no option and ignores this one: it answers ``"logprobs": m`` up to 8."""
+    needs no option and ignores this one: it answers ``"logprobs": m`` up to 8.
+    ``logit_processors=True`` (with ``continuous=True``): the engine keeps the per-slot tables
+    of the repetition / presence / frequency penalties, ``logit_bias`` and
+    ``min_new_tokens``, and a request may name them; the static server needs no option."""
     if continuous:
         dep = deployment(GPT2EngineServer, name="GPT2EngineServer")
         return dep.bind(config, state_dict_path, seed, slots, eos_token_id, device, None,
-                        prefixes, prefill_chunk, adapters, lora_rank, speculate, ngram, logprobs)
+                        prefixes, prefill_chunk, adapters, lora_rank, speculate, ngram, logprobs,
+                        logit_processors)
     if prefixes or prefill_chunk is not None or adapters or speculate:
         raise ValueError("prefixes, prefill_chunk, adapters and speculate need continuous=True")
     dep = deployment(GPT2Server, name="GPT2Server")
