@@ -38,6 +38,10 @@ MI355X-first choices:
   (``generate(..., repetition_penalty=, ...)``) are edits of the logits buffer by
   ``rf.logit_process`` (ops/csrc/logit_proc.hip) before the sampler reads it, on the device
   and inside the captured step.
+  Grammar-constrained decoding (``generate(..., grammar=TokenDFA)``, models/grammar.py): each
+  row's automaton state lives on the device, ``rf.grammar_advance`` follows the token just
+  emitted and ``rf.grammar_mask`` (ops/csrc/grammar.hip) bans what the state does not allow,
+  after the logit processors and before the sampler, inside the captured step as well.
   The three inference passes (prompt, extend, decode) run ONE layer loop, ``_layers``, and
   hand it their attention step; the training ``forward`` keeps its own (autograd ops).
 """
@@ -51,6 +55,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from ray_amd.models.grammar import TokenDFA
 from ray_amd.ops import functional as rf
 from ray_amd.ops.graph_lock import CapturedStep
 
@@ -181,7 +186,7 @@ class _SeededSampler:
     and a token then costs one replay."""
 
     def __init__(self, model, cache, logits, out, temperature, top_k, top_p, seeds, eos,
-                 adapters=None, logprobs=None, controls=None):
+                 adapters=None, logprobs=None, controls=None, grammar=None):
         cfg = model.cfg
         dev = out.device
         B = out.shape[0]
@@ -205,11 +210,20 @@ class _SeededSampler:
         # controls=(LogitControls, ...): the logits buffer holds PROCESSED logits whenever the
         # sampler reads it (rf.logit_process on the prefill's here, on decode_step's in _step);
         # n_out counts the tokens in ``out``, advanced where ``col`` is (None: no such call)
-        self.ctl = None
-        if controls is not None:
-            self.ctl = controls
+        self.ctl = controls
+        if controls is not None or grammar is not None:
             self.n_out = torch.zeros(B, dtype=torch.int32, device=dev)
+        if controls is not None:
             self.ctl.process(self.logits, self.out, self.n_out, self.eos)
+        # grammar=(table int16 [N, Vt], start states int32 [B]): each row's automaton state and
+        # the number of tokens of ``out`` it has consumed; the buffer holds MASKED logits
+        # whenever the sampler reads it (None: no such call)
+        self.gtable = None
+        if grammar is not None:
+            self.gtable, start = grammar
+            self.gstate = start.clone()
+            self.gpos = torch.zeros(B, dtype=torch.int32, device=dev)
+            rf.grammar_mask(self.logits, self.gtable, self.gstate)
         self.tok = None  # the sampler's output (inside a capture: the graph's static buffer)
         self.graph = None
 
@@ -230,9 +244,14 @@ class _SeededSampler:
         if self.lp is not None:
             self.cols += 1
         self.model.decode_step(self.tok, self.cache, out=self.buf, adapters=self.adapters)
-        if self.ctl is not None:
+        if self.ctl is not None or self.gtable is not None:
             self.n_out += 1  # ``out`` already holds the token just drawn
+        if self.gtable is not None:
+            rf.grammar_advance(self.gstate, self.gpos, self.out, self.n_out, self.gtable, 1)
+        if self.ctl is not None:
             self.ctl.process(self.logits, self.out, self.n_out, self.eos)
+        if self.gtable is not None:
+            rf.grammar_mask(self.logits, self.gtable, self.gstate)
 
     def draw_last(self):
         """The last token of a call needs no ``decode_step`` after it."""
@@ -357,6 +376,42 @@ class LogitControls:
                                 self.repetition, self.presence, self.frequency, self.min_new,
                                 self.bias_ids, self.bias_vals, self.n_bias, eos_token_id=eos,
                                 **kw)
+
+
+def checked_grammar(dfa, vocab_size, eos_token_id, controls=None):
+    """One request's grammar, checked against the model and the request's ``checked_controls``
+    result: ``ValueError`` for anything but a ``TokenDFA`` over this vocabulary that ends
+    with this EOS, and for the two controls that can leave a row with no allowed token
+    (``min_new_tokens > 0`` bans EOS, a ``-inf`` ``logit_bias`` bans a token), which the
+    sampler declares out of contract."""
+    if not isinstance(dfa, TokenDFA):
+        raise ValueError(f"grammar must be a TokenDFA, got {type(dfa).__name__}")
+    if eos_token_id is None:
+        raise ValueError("grammar needs eos_token_id")
+    if dfa.vocab_size != vocab_size or dfa.eos_token_id != int(eos_token_id):
+        raise ValueError(f"grammar is over {dfa.vocab_size} tokens with EOS "
+                         f"{dfa.eos_token_id}, the request over {vocab_size} with EOS "
+                         f"{eos_token_id}")
+    if controls is not None:
+        if controls[3] > 0:
+            raise ValueError("grammar and min_new_tokens > 0 cannot go together: the grammar "
+                             "decides where EOS is allowed")
+        if any(v == float("-inf") for _, v in controls[4]):
+            raise ValueError("grammar and a -inf logit_bias cannot go together: no allowed "
+                             "token might be left")
+    return dfa
+
+
+def grammar_table(dfas):
+    """One device table for several automata: ``(int16 numpy [N, Vt], [first row of each])``,
+    every automaton's states shifted to its rows."""
+    import numpy as np
+
+    offs, n = [], 0
+    for d in dfas:
+        offs.append(n)
+        n += d.n_states
+    return np.concatenate([d.table(o) for d, o in zip(dfas, offs)]), offs
 
 
 def _per_row(name, value, default, B, cast):
@@ -688,7 +743,7 @@ class GPT2(nn.Module):
     def generate(self, idx, max_new_tokens, *, lens=None, temperature=0.0, top_k=None,
                  top_p=None, seeds=None, eos_token_id=None, generator=None, graph=False,
                  adapters=None, logprobs=None, repetition_penalty=None, presence_penalty=None,
-                 frequency_penalty=None, min_new_tokens=None, logit_bias=None):
+                 frequency_penalty=None, min_new_tokens=None, logit_bias=None, grammar=None):
         """Autoregressive generation with a KV cache: ``idx`` [B, T] prompts, right-padded
         to a common length with true lengths ``lens`` (default: all T). Returns the new
         tokens [B, max_new_tokens] (int64). ``temperature`` 0 is greedy, otherwise samples
@@ -728,7 +783,19 @@ class GPT2(nn.Module):
         on the device and inside the captured step: a row's tokens still depend on that row
         alone and a token still costs one replay. ``logprobs=`` then reports the
         distribution the token was drawn from, the processed logits. With none of them
-        given not one extra op runs and the results are what they were."""
+        given not one extra op runs and the results are what they were.
+
+        ``grammar`` (a ``TokenDFA`` of models/grammar.py, or one per row with None for an
+        unconstrained row; needs ``seeds=`` and ``eos_token_id``): the row's output is a word
+        of the grammar followed by EOS, or a prefix of one where ``max_new_tokens`` cuts it,
+        for every sampling setting. The distinct automata share one int16 table on the device
+        (about 100 KB per state at GPT-2's vocabulary); ``rf.grammar_advance`` follows each
+        emitted token and ``rf.grammar_mask`` sets the logits of the tokens the state does not
+        allow to ``-inf``, after the logit processors and before the sampler, inside the
+        captured step: a token still costs one replay, and ``logprobs=`` reports the masked
+        distribution. ``min_new_tokens > 0`` or a ``-inf`` ``logit_bias`` on a row with a
+        grammar is a ``ValueError`` (either could leave no token). Without ``grammar`` not
+        one extra op runs."""
         cfg = self.cfg
         B, T = idx.shape
         if logprobs is not None:
@@ -744,6 +811,8 @@ class GPT2(nn.Module):
                 raise ValueError("top_p needs the device sampler: pass seeds=")
             for k in named:
                 raise ValueError(f"{k} needs the device sampler: pass seeds=")
+            if grammar is not None:
+                raise ValueError("grammar needs the device sampler: pass seeds=")
             if any(isinstance(v, (list, tuple, torch.Tensor)) for v in (temperature, top_k)):
                 raise ValueError("per-row temperature / top_k need the device sampler: pass "
                                  "seeds=")
@@ -776,7 +845,7 @@ class GPT2(nn.Module):
         if graph and not idx.is_cuda:
             raise ValueError("graph=True needs the model and prompts on the GPU")
         dev = idx.device
-        ctl = None
+        ctl = rows_c = None
         if named:
             cols = {k: _per_row(k, v, None, B, lambda x: x) if k != "logit_bias" or
                     not isinstance(v, dict) else [v] * B for k, v in named.items()}
@@ -787,6 +856,21 @@ class GPT2(nn.Module):
             idx_l = idx.tolist()
             ctl.put(torch.arange(B, device=dev), rows_c,
                     [idx_l[b][: lens_l[b]] for b in range(B)])
+        gram = None
+        if grammar is not None:
+            per_row = _per_row("grammar", grammar, None, B, lambda x: x)
+            dfas = []
+            for b, d in enumerate(per_row):
+                if d is not None and not any(d is e for e in dfas):
+                    dfas.append(checked_grammar(d, cfg.vocab_size, eos_token_id))
+                if d is not None and rows_c is not None:
+                    checked_grammar(d, cfg.vocab_size, eos_token_id, rows_c[b])
+            if dfas:
+                table, offs = grammar_table(dfas)
+                first = {id(d): o + d.start for d, o in zip(dfas, offs)}
+                start = [rf.GRAMMAR_NONE if d is None else first[id(d)] for d in per_row]
+                gram = (torch.from_numpy(table).to(dev),
+                        torch.tensor(start, dtype=torch.int32, device=dev))
         cache = KVCache(cfg, B, max(lens_l) + max_new_tokens, dev, self.wte.dtype)
         logits = self.prefill(idx, torch.tensor(lens_l, dtype=torch.int32, device=dev), cache,
                               adapters=ad)
@@ -794,7 +878,7 @@ class GPT2(nn.Module):
         if seeds is not None:
             eos = None if eos_token_id is None else int(eos_token_id)
             step = _SeededSampler(self, cache, logits, out, temps, ks, ps, seeds_l, eos, ad,
-                                  logprobs, ctl)
+                                  logprobs, ctl, gram)
             res = out if logprobs is None else (out,) + step.lp
             if max_new_tokens > 1:
                 step()

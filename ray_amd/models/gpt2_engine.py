@@ -109,6 +109,33 @@ was drawn from) are those of ``generate(..., seeds=[seed], <same controls>)`` on
 cut after the first EOS, with prefixes, chunked prefill, adapters, ``cancel``, every
 ``speculate`` and ``logprobs``; a request that names no control is untouched.
 
+Grammar-constrained decoding (``grammar_states=N``; 0, the default, is the engine without it:
+no buffer, no extra op, and ``submit`` rejects ``grammar=``): a pool ``gtable`` int16 [N, Vt]
+of automaton states (``TokenDFA`` rows, models/grammar.py; Vt is the vocabulary rounded up to
+8, so the pool costs about 100 KB per state at GPT-2's vocabulary) and per slot ``gstate``
+(the automaton state, ``rf.GRAMMAR_NONE`` for a request without a grammar) and ``gpos`` (the
+output tokens that state has consumed), all at fixed addresses. ``add_grammar(dfa)`` writes
+the automaton's states, shifted to pool-global ids, into the first free range of rows that
+fits, in place between steps and with no re-capture; ``submit(..., grammar=gid)`` names it;
+``drop_grammar(gid)`` frees the rows once no queued or running request names it. When a slot's
+prompt is complete, after the logit processors, ``gstate`` becomes the grammar's start state
+and ``rf.grammar_mask`` bans what it does not allow in that round's prefill rows before they
+go into ``self.buf``. The invariant: ``self.buf`` holds processed AND MASKED rows. The plain
+step keeps it at its end: ``rf.grammar_advance`` (one step: the token ``slot_advance`` just
+stored), the logit processors, then ``rf.grammar_mask`` on ``self.logits`` with ``active``.
+The speculative step masks the window's logits between the logit processors and the window's
+sampler: window row j of a slot uses the slot's state walked over ``win[slot, :j + 1]``, and
+is live iff ``j < n_win`` and the slot is active; ``rf.grammar_advance`` (up to k + 1 steps)
+follows what ``rf.spec_accept`` kept. That is exact: a draft the grammar forbids leaves its
+own row and all later rows of the window unmasked, but it can never equal ``cand`` of the
+masked row before it, so it and everything after it is rejected; and the row ``spec_accept``
+copies into ``self.buf`` was walked over accepted tokens only, so it is already masked. Every
+constrained request's output is a word of its grammar (a prefix where ``max_new_tokens`` cuts
+it), and its tokens and logprobs are those of ``generate(..., seeds=[seed], grammar=dfa, <same
+controls>)`` on it alone, with prefixes, chunked prefill, adapters, ``cancel``, ``logprobs``,
+logit processors and every ``speculate``; a request without a grammar gets the tokens it got
+before, whoever shares the step.
+
 Single-threaded by contract: every call comes from one thread."""
 
 from __future__ import annotations
@@ -119,17 +146,19 @@ import math
 import numpy as np
 import torch
 
-from ray_amd.models.gpt2 import GPT2, KVCache, LogitControls, checked_controls
+from ray_amd.models.gpt2 import (GPT2, KVCache, LogitControls, checked_controls,
+                                 checked_grammar)
+from ray_amd.models.grammar import MAX_STATES, padded_vocab
 from ray_amd.ops import functional as rf
 from ray_amd.ops.graph_lock import CapturedStep
 
 
 class _Request:
     __slots__ = ("rid", "tokens", "max_new", "temperature", "top_k", "top_p", "seed", "pid",
-                 "adapter", "logprobs", "controls")
+                 "adapter", "logprobs", "controls", "grammar")
 
     def __init__(self, rid, tokens, max_new, temperature, top_k, top_p, seed, pid=None,
-                 adapter=-1, logprobs=None, controls=None):
+                 adapter=-1, logprobs=None, controls=None, grammar=None):
         # tokens: the whole prompt (the prefix's tokens included); pid: the prefix it names
         self.rid, self.tokens, self.max_new = rid, tokens, max_new
         self.temperature, self.top_k, self.top_p, self.seed = temperature, top_k, top_p, seed
@@ -137,12 +166,14 @@ class _Request:
         self.adapter = adapter  # -1: the base model
         self.logprobs = logprobs  # None: the request reports none; else its top-n width
         self.controls = controls  # a checked_controls result (None: neutral)
+        self.grammar = grammar  # an add_grammar id (None: unconstrained)
 
 
 class GPT2Engine:
     def __init__(self, model: GPT2, slots=8, max_len=None, eos_token_id=None, graph=None,
                  poll_every=8, prefix_slots=0, prefill_chunk=None, lora=None, speculate=0,
-                 ngram=(2, 4), drafter=None, logprobs=None, logit_processors=False):
+                 ngram=(2, 4), drafter=None, logprobs=None, logit_processors=False,
+                 grammar_states=0):
         cfg = model.cfg
         dev = model.wte.device
         S = int(slots)
@@ -170,6 +201,12 @@ class GPT2Engine:
                                      or not 0 <= logprobs <= rf.LOGPROB_MAX_TOP):
             raise ValueError(f"logprobs must be None or an int in 0..{rf.LOGPROB_MAX_TOP}, got "
                              f"{logprobs!r}")
+        if isinstance(grammar_states, bool) or not isinstance(grammar_states, int) or \
+                not 0 <= grammar_states <= MAX_STATES:
+            raise ValueError(f"grammar_states must be an int in 0..{MAX_STATES}, got "
+                             f"{grammar_states!r}")
+        if grammar_states and eos_token_id is None:
+            raise ValueError("grammar_states needs eos_token_id: a grammar ends with EOS")
         if graph is None:
             graph = dev.type == "cuda"
         if graph and dev.type != "cuda":
@@ -243,6 +280,23 @@ class GPT2Engine:
                 self._ctl_n_extra = torch.arange(1, W + 1, dtype=torch.int32,
                                                  device=dev).repeat(S)
 
+        if grammar_states:
+            # the pool of automaton states and every slot's state: fixed addresses, rewritten
+            # in place (add_grammar, _fill_rows); the attributes exist only with the option
+            self.gtable = torch.full((grammar_states, padded_vocab(cfg.vocab_size)), -1,
+                                     dtype=torch.int16, device=dev)
+            self.gstate = torch.full((S,), rf.GRAMMAR_NONE, dtype=torch.int32, device=dev)
+            self.gpos = torch.zeros(S, dtype=torch.int32, device=dev)
+            self._gfree = [(0, grammar_states)]  # free ranges (first row, rows), by first row
+            self._grammars = {}  # gid -> (first row, rows, the start state's pool id, dfa)
+            self._next_gid = 0
+            if speculate:
+                W = speculate + 1
+                self._g_rows = self.cache.rows.repeat_interleave(W)
+                self._g_idx = torch.arange(W, dtype=torch.int32, device=dev).unsqueeze(0)
+                self._g_n_extra = torch.arange(1, W + 1, dtype=torch.int32, device=dev).repeat(S)
+        self._has_grammar = bool(grammar_states)
+
         self._queue = collections.deque()
         self._slot_req = [None] * S  # the request running in each slot
         self._seen_host = [0] * S
@@ -277,9 +331,15 @@ class GPT2Engine:
         rf.slot_advance(tok, self.cache.lens, self.n_out, self.max_new, self.active, self.out,
                         self.eos)
         self.model.decode_step(tok, self.cache, out=self.buf, adapters=self.adapter)
+        if self._has_grammar:
+            # the state follows tok (a slot without a grammar, or one that is idle and has
+            # nothing new in out, stays as it is)
+            rf.grammar_advance(self.gstate, self.gpos, self.out, self.n_out, self.gtable, 1)
         if self.ctl is not None:
             # out / n_out hold tok, and a slot that just finished is inactive
             self.ctl.process(self.logits, self.out, self.n_out, self.eos, active=self.active)
+        if self._has_grammar:
+            rf.grammar_mask(self.logits, self.gtable, self.gstate, active=self.active)
 
     def _ngram_drafter(self, tok0, hist, lens, n_out, max_new, active):
         return rf.spec_draft(tok0, hist, lens, n_out, max_new, active, self.speculate,
@@ -302,6 +362,14 @@ class GPT2Engine:
                              extra=win.unsqueeze(1).expand(S, W, W).reshape(S * W, W),
                              n_extra=self._ctl_n_extra,
                              active=live.to(torch.uint8).view(S * W))
+        if self._has_grammar:
+            # window row j: the slot's state walked over win[s, :j + 1]; a forbidden draft
+            # leaves its row and the later ones unmasked, and is rejected by the row before
+            live = (self._g_idx < n_win.unsqueeze(1)) & self.active.bool().unsqueeze(1)
+            rf.grammar_mask(self.logits_win.view(S * W, -1)[:, :V], self.gtable, self.gstate,
+                            rows=self._g_rows,
+                            extra=win.unsqueeze(1).expand(S, W, W).reshape(S * W, W),
+                            n_extra=self._g_n_extra, active=live.to(torch.uint8).view(S * W))
         temperature, top_k, top_p, seeds = (t.view(S * W) for t in self._win_params)
         # window row i holds the logits at position lens + 1 + i
         cand = rf.sample_logits(self.logits_win.view(S * W, -1)[:, :V], temperature, top_k, top_p,
@@ -322,6 +390,8 @@ class GPT2Engine:
         rf.spec_accept(win, n_win, cand.view(S, W), self.logits_win, lens, self.n_out,
                        self.max_new, self.active, self.out, self.hist, self.buf, self.n_drafted,
                        self.n_accepted, self.eos)
+        if self._has_grammar:
+            rf.grammar_advance(self.gstate, self.gpos, self.out, self.n_out, self.gtable, W)
 
     def spec_stats(self):
         """``{"drafted": n, "accepted": m}``: the draft tokens the verify passes checked so
@@ -390,6 +460,58 @@ class GPT2Engine:
             raise ValueError(f"adapter {i} is in use")
         self.lora.clear(i)
 
+    def _need_pool(self, what):
+        if not self._has_grammar:
+            raise ValueError(f"{what}, but the engine has no grammar pool: grammar_states=")
+
+    @property
+    def grammar_free(self):
+        """Free rows (automaton states) of the grammar pool."""
+        self._need_pool("grammar_free")
+        return sum(n for _, n in self._gfree)
+
+    def add_grammar(self, dfa):
+        """Writes ``dfa`` (a ``TokenDFA`` over the model's vocabulary that ends with the
+        engine's ``eos_token_id``) into the first free range of pool rows that holds its
+        states, IN PLACE between steps: no re-capture. Returns the grammar's id for
+        ``submit(..., grammar=gid)``. ``ValueError`` for a bad automaton or when no free range
+        is long enough; the pool then holds what it held."""
+        self._need_pool("add_grammar")
+        checked_grammar(dfa, self.model.cfg.vocab_size, self.eos)
+        n = dfa.n_states
+        for i, (first, rows) in enumerate(self._gfree):
+            if rows >= n:
+                break
+        else:
+            raise ValueError(f"the grammar pool is full: no free range of {n} states "
+                             f"({self.grammar_free} of {self.gtable.shape[0]} rows are free)")
+        table = torch.from_numpy(dfa.table(first))
+        self.gtable[first: first + n].copy_(table)
+        self._gfree[i: i + 1] = [(first + n, rows - n)] if rows > n else []
+        gid = self._next_gid
+        self._next_gid += 1
+        self._grammars[gid] = (first, n, first + dfa.start, dfa)
+        return gid
+
+    def drop_grammar(self, gid):
+        """Frees the grammar's rows of the pool. ``ValueError`` for an unknown id, or while a
+        queued or running request names it."""
+        self._need_pool("drop_grammar")
+        if isinstance(gid, bool) or not isinstance(gid, int) or gid not in self._grammars:
+            raise ValueError(f"unknown grammar {gid!r}")
+        if any(r.grammar == gid for r in self._queue) or \
+                any(r is not None and r.grammar == gid for r in self._slot_req):
+            raise ValueError(f"grammar {gid} is in use")
+        first, n = self._grammars.pop(gid)[:2]
+        free = sorted(self._gfree + [(first, n)])
+        merged = [free[0]]
+        for f, m in free[1:]:
+            if merged[-1][0] + merged[-1][1] == f:
+                merged[-1] = (merged[-1][0], merged[-1][1] + m)
+            else:
+                merged.append((f, m))
+        self._gfree = merged
+
     def add_prefix(self, tokens, adapter=None):
         """Prefills ``tokens`` (1 <= len < max_len) once into a row of the prefix store and
         returns the prefix's id for ``submit(..., prefix=pid)``. ``ValueError`` for bad
@@ -425,7 +547,7 @@ class GPT2Engine:
     def submit(self, tokens, max_new_tokens, temperature=0.0, top_k=None, top_p=None, seed=0,
                prefix=None, adapter=None, logprobs=None, repetition_penalty=None,
                presence_penalty=None, frequency_penalty=None, logit_bias=None,
-               min_new_tokens=None):
+               min_new_tokens=None, grammar=None):
         """Queues a request and returns its id; a bad request raises ``ValueError`` and
         queues nothing. ``prefix``: an ``add_prefix`` id; ``tokens`` is then the non-empty
         continuation and the request's prompt is the prefix's tokens followed by it.
@@ -435,8 +557,16 @@ class GPT2Engine:
         the request's events carry the log-probability of every token and the ``logprobs``
         most likely tokens at its position (None: they carry none). ``repetition_penalty``,
         ``presence_penalty``, ``frequency_penalty``, ``logit_bias`` and ``min_new_tokens``: as
-        in ``generate``, on an engine built with ``logit_processors=True``."""
+        in ``generate``, on an engine built with ``logit_processors=True``. ``grammar``: an
+        ``add_grammar`` id on an engine built with ``grammar_states=N``: the output is a word
+        of that grammar; not together with ``min_new_tokens > 0`` or a ``-inf``
+        ``logit_bias``."""
         tokens = self._checked_tokens(tokens, "request")
+        if grammar is not None:
+            self._need_pool("grammar given")
+            if isinstance(grammar, bool) or not isinstance(grammar, int) or \
+                    grammar not in self._grammars:
+                raise ValueError(f"unknown grammar {grammar!r}")
         controls = {"repetition_penalty": repetition_penalty,
                     "presence_penalty": presence_penalty,
                     "frequency_penalty": frequency_penalty, "logit_bias": logit_bias,
@@ -482,10 +612,13 @@ class GPT2Engine:
             seed -= 2 ** 64
         top_k = max(0, min(top_k, 2 ** 31 - 1))
         controls = checked_controls(self.model.cfg.vocab_size, max_new, self.eos, **controls)
+        if grammar is not None:  # the combinations that could leave a row no token
+            checked_grammar(self._grammars[grammar][3], self.model.cfg.vocab_size, self.eos,
+                            controls)
         rid = self._next_rid
         self._next_rid += 1
         self._queue.append(_Request(rid, tokens, max_new, temperature, top_k, top_p, seed,
-                                    prefix, adapter, logprobs, controls))
+                                    prefix, adapter, logprobs, controls, grammar))
         return rid
 
     def cancel(self, rid):
@@ -563,7 +696,9 @@ class GPT2Engine:
             idx[b, : lens[b]] = torch.tensor(r.tokens[bases[b]: bases[b] + lens[b]],
                                              dtype=torch.long)
         # three uploads per round and path, however many requests it feeds
-        ints = torch.tensor([[s, n, r.top_k, r.max_new, r.seed, b, r.adapter]
+        ints = torch.tensor([[s, n, r.top_k, r.max_new, r.seed, b, r.adapter,
+                              rf.GRAMMAR_NONE if r.grammar is None
+                              else self._grammars[r.grammar][2]]
                              for s, n, r, b in zip(rows, lens, reqs, bases)],
                             dtype=torch.int64).to(dev)
         flts = torch.tensor([[r.temperature, r.top_p] for r in reqs],
@@ -595,6 +730,12 @@ class GPT2Engine:
             # round's rows: self.buf only ever holds processed logits
             self.ctl.put(sl, [reqs[j].controls for j in done], [reqs[j].tokens for j in done])
             self.ctl.process(logits, self.out, self.n_out, self.eos, rows=sl.to(torch.int32))
+        if self._has_grammar:
+            # the slots' start states (GRAMMAR_NONE without a grammar), then this round's
+            # rows: self.buf only ever holds masked logits
+            self.gstate.index_copy_(0, sl, ints[:, 7].to(torch.int32))
+            self.gpos.index_fill_(0, sl, 0)
+            rf.grammar_mask(logits, self.gtable, self.gstate, rows=sl.to(torch.int32))
         self.logits.index_copy_(0, sl, logits)
         self.top_k.index_copy_(0, sl, ints[:, 2].to(torch.int32))
         self.max_new.index_copy_(0, sl, ints[:, 3].to(torch.int32))

@@ -139,6 +139,11 @@ _SIGS = {
     "ra_logit_process_max_bias": [],
     "ra_logit_process_max_context": [],
     "ra_logit_process": [c_void_p, c_long] + [c_void_p] * 15 + [c_int] * 8 + [c_void_p],
+    "ra_grammar_max_walk": [],
+    "ra_grammar_max_states": [],
+    "ra_grammar_mask_chunk": [c_int, c_int],
+    "ra_grammar_mask": [c_void_p, c_long] + [c_void_p] * 6 + [c_int] * 7 + [c_void_p],
+    "ra_grammar_advance": [c_void_p] * 5 + [c_int] * 5 + [c_void_p],
     "ra_gemm_nt": [c_void_p, c_long, c_void_p, c_long, c_void_p, c_long, c_int, c_int, c_int,
                    c_int, c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_int, c_int,
                    c_void_p],

@@ -1270,6 +1270,131 @@ def logit_process(logits, prompt, prompt_len, out, n_out, repetition, presence, 
     return logits
 
 
+from ray_amd.models.grammar import GRAMMAR_DEAD, GRAMMAR_NONE  # noqa: E402,F401  (a row's state)
+from ray_amd.models.grammar import MAX_STATES as GRAMMAR_MAX_STATES  # noqa: E402
+
+GRAMMAR_MAX_WALK = 16  # ops/csrc/grammar.hip kMaxWalk (checked against the library, once)
+_grammar_lib = None
+
+
+def _grammar_library():
+    """The library, its grammar limits checked against this module's the first time."""
+    global _grammar_lib
+    if _grammar_lib is None:
+        L = _lib.lib()
+        assert L.ra_grammar_max_walk() == GRAMMAR_MAX_WALK
+        assert L.ra_grammar_max_states() == GRAMMAR_MAX_STATES
+        _grammar_lib = L
+    return _grammar_lib
+
+
+def _grammar_table(op, table, like):
+    if not isinstance(table, torch.Tensor) or table.dim() != 2 or table.dtype != torch.int16 \
+            or table.device != like.device or table.shape[0] < 1 or table.shape[1] % 8 or \
+            table.shape[0] > GRAMMAR_MAX_STATES:
+        raise ValueError(f"{op}: table must be an int16 tensor [N <= {GRAMMAR_MAX_STATES}, Vt] "
+                         f"on {like.device} with Vt a multiple of 8")
+    return table.shape
+
+
+def grammar_advance(state, pos, out, n_out, table, max_steps):
+    """Follows each row's emitted tokens through its token DFA: while ``pos[r] < n_out[r]``,
+    at most ``max_steps`` times, ``state[r] = table[state[r], out[r, pos[r]]]`` and ``pos[r]
+    += 1``; a token the state does not allow makes it ``GRAMMAR_DEAD``. ``state``, ``pos``
+    int32 [R] are edited IN PLACE and returned; ``out`` int64 [R, cap], ``n_out`` int32 [R],
+    ``table`` int16 [N, Vt]. Semantics: ``reference.grammar_advance``, bit for bit.
+
+    HIP kernel (ops/csrc/grammar.hip: one launch, one thread per row, every index checked on
+    the device, no host sync, capturable) for GPU tensors; CPU tensors use the reference."""
+    op = "grammar_advance"
+    if not isinstance(out, torch.Tensor) or out.dim() != 2 or out.shape[0] < 1 or \
+            out.shape[1] < 1 or out.dtype != torch.int64:
+        raise ValueError(f"{op}: out must be an int64 tensor [R, cap]")
+    R, cap = out.shape
+    N, Vt = _grammar_table(op, table, out)
+    for name, t in (("state", state), ("pos", pos), ("n_out", n_out)):
+        _int_vec(name, op, t, R, out)
+    if isinstance(max_steps, bool) or not isinstance(max_steps, int) or max_steps < 0:
+        raise ValueError(f"{op}: max_steps must be an int >= 0, got {max_steps!r}")
+    for name, t in (("state", state), ("pos", pos)):
+        if not t.is_contiguous():
+            raise ValueError(f"{op}: {name} is written in place and must be contiguous")
+    if not _hip(out):
+        return ref.grammar_advance(state, pos, out, n_out, table, max_steps)
+    L = _grammar_library()
+    c = torch.Tensor.contiguous
+    check(L.ra_grammar_advance(ptr(state), ptr(pos), ptr(c(out)), ptr(c(n_out)), ptr(c(table)),
+                               R, cap, N, Vt, max_steps, stream_ptr()), op)
+    return state, pos
+
+
+def grammar_mask(logits, table, state, rows=None, extra=None, n_extra=None, active=None,
+                 vocab_size=None, chunk=0):
+    """Bans, IN PLACE, the tokens that each row's grammar state does not allow: element ``i <
+    V`` of row b of ``logits`` [B, Vs] (``V = vocab_size or Vs``) becomes ``-inf`` when
+    ``table[q, i] < 0``, q being ``state[rows[b]]`` (``state`` int32 [R]; ``rows`` int32 [B],
+    default b) walked over ``extra[b, :n_extra[b]]`` (int64 [B, W], int32 [B]) through
+    ``table`` int16 [N, Vt >= V]. A row with ``active[b] == 0`` (uint8 [B]), a context row or
+    state out of range (``GRAMMAR_NONE`` and ``GRAMMAR_DEAD`` are), or whose walk meets a token
+    that is not allowed keeps all its bytes; so does every element that is allowed and every
+    column at or beyond V. Semantics: ``reference.grammar_mask``, bit for bit. Returns
+    ``logits``.
+
+    HIP kernel (ops/csrc/grammar.hip: one launch over (row, chunk of columns), nothing read on
+    the host, no workspace, capturable) for GPU tensors with bf16 logits of unit column stride,
+    at most ``SAMPLE_MAX_VOCAB`` columns, ``W <= GRAMMAR_MAX_WALK`` and a 16-byte aligned
+    contiguous table; the rows may be a column slice of a wider buffer at any 2-byte
+    alignment, edited in place. ``chunk`` (16-byte slots of a row per workgroup, a multiple of
+    256; 0: the library's choice) is there for measurements. Everything else uses the
+    plain-torch reference."""
+    op = "grammar_mask"
+    if not isinstance(logits, torch.Tensor) or logits.dim() != 2:
+        raise ValueError(f"{op}: logits must be [B, V]")
+    B, Vs = logits.shape
+    V = Vs if vocab_size is None else int(vocab_size)
+    if B < 1 or V < 1 or V > Vs:
+        raise ValueError(f"{op}: vocab_size {V} does not fit logits {tuple(logits.shape)}")
+    if logits.dtype not in ref._BITS:
+        raise ValueError(f"{op}: logits must be floating point")
+    N, Vt = _grammar_table(op, table, logits)
+    if Vt < V:
+        raise ValueError(f"{op}: table rows of {Vt} columns do not cover vocab_size {V}")
+    if not isinstance(state, torch.Tensor) or state.dim() != 1 or state.shape[0] < 1:
+        raise ValueError(f"{op}: state must be an int32 tensor [R]")
+    R = state.shape[0]
+    _int_vec("state", op, state, R, logits)
+    if rows is None:
+        if R < B:
+            raise ValueError(f"{op}: {B} logits rows need rows= to share {R} context rows")
+    else:
+        _int_vec("rows", op, rows, B, logits)
+    W = 0
+    if (extra is None) != (n_extra is None):
+        raise ValueError(f"{op}: extra and n_extra go together")
+    if extra is not None:
+        if not isinstance(extra, torch.Tensor) or extra.dim() != 2:
+            raise ValueError(f"{op}: extra must be an int64 tensor [B, W]")
+        W = extra.shape[1]
+        _table("extra", op, extra, (B, W), logits, torch.int64)
+        _int_vec("n_extra", op, n_extra, B, logits)
+    if active is not None:
+        _int_vec("active", op, active, B, logits, torch.uint8)
+    hip = _hip(logits) and logits.dtype == torch.bfloat16 and V <= SAMPLE_MAX_VOCAB and \
+        logits.stride(1) == 1 and (B == 1 or logits.stride(0) >= V) and \
+        W <= GRAMMAR_MAX_WALK and (extra is None or W > 0) and table.is_contiguous() and \
+        table.data_ptr() % 16 == 0
+    if not hip:
+        return ref.grammar_mask(logits, table, state, rows, extra, n_extra, active, V)
+    L = _grammar_library()
+    c = torch.Tensor.contiguous
+    check(L.ra_grammar_mask(
+        ptr(logits), max(logits.stride(0), V), ptr(table), ptr(c(state)),
+        ptr(None if rows is None else c(rows)), ptr(None if active is None else c(active)),
+        ptr(None if extra is None else c(extra)), ptr(None if extra is None else c(n_extra)),
+        B, V, N, Vt, R, W, int(chunk), stream_ptr()), op)
+    return logits
+
+
 # --------------------------------------------------------------------- cross entropy
 class _CrossEntropy(torch.autograd.Function):
     @staticmethod

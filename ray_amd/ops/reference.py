@@ -596,6 +596,81 @@ def logit_process(logits, prompt, prompt_len, out, n_out, repetition, presence, 
     return logits
 
 
+from ray_amd.models.grammar import GRAMMAR_DEAD, GRAMMAR_NONE  # noqa: E402  (a row's state)
+
+
+def grammar_advance(state, pos, out, n_out, table, max_steps):
+    """Follows the emitted tokens through a token DFA (ops/csrc/grammar.hip semantics): the
+    single definition. Edits ``state`` and ``pos`` (int32 [R]) IN PLACE. No host sync.
+
+    ``table`` int16 [N, Vt]: ``table[q, t]`` is the state after token t in state q, negative
+    when t is not allowed there. ``out`` int64 [R, cap] with ``n_out`` int32 [R] holds each
+    row's tokens; ``pos[r]`` counts those ``state[r]`` has consumed. Per row, at most
+    ``max_steps`` times while ``pos[r] < n_out[r]``: ``state[r] = table[state[r],
+    out[r, pos[r]]]`` and ``pos[r] += 1``; a result outside ``[0, N)`` makes the state
+    ``GRAMMAR_DEAD``. A row whose state is outside ``[0, N)`` (``GRAMMAR_NONE`` and
+    ``GRAMMAR_DEAD`` included), whose ``pos`` is negative, whose ``n_out`` exceeds cap or
+    whose next token is outside ``[0, Vt)`` is left alone from there on."""
+    N, Vt = table.shape
+    cap = out.shape[1]
+    n = n_out.long()
+    for _ in range(int(max_steps)):
+        s, p = state.long(), pos.long()
+        live = (s >= 0) & (s < N) & (p >= 0) & (p < n) & (n <= cap)
+        tok = out.gather(1, p.clamp(0, cap - 1).unsqueeze(1)).squeeze(1)
+        live = live & (tok >= 0) & (tok < Vt)
+        nx = table[s.clamp(0, N - 1), tok.clamp(0, Vt - 1)].to(torch.int32)
+        nx = torch.where((nx < 0) | (nx >= N), torch.full_like(nx, GRAMMAR_DEAD), nx)
+        state.copy_(torch.where(live, nx, state))
+        pos.copy_(torch.where(live, pos + 1, pos))
+    return state, pos
+
+
+def grammar_mask(logits, table, state, rows=None, extra=None, n_extra=None, active=None,
+                 vocab_size=None):
+    """Bans the tokens a row's grammar state does not allow (ops/csrc/grammar.hip semantics):
+    the single definition. Edits ``logits`` IN PLACE and returns it. No host sync.
+
+    ``logits`` [B, Vs], of which the first ``V = vocab_size or Vs`` columns count; ``table``
+    int16 [N, Vt >= V] as in ``grammar_advance``; ``state`` int32 [R]. The state q of logits
+    row b is ``state[rows[b]]`` (``rows`` int32 [B], default b) walked over ``extra[b,
+    :n_extra[b]]`` (int64 [B, W], int32 [B]; a speculative window up to the row's position).
+    Every element ``i < V`` with ``table[q, i] < 0`` becomes ``-inf`` (0xFF80 for bf16); every
+    other byte of the buffer keeps its bits. A row keeps all its bytes when ``active[b] ==
+    0``, ``rows[b]`` is outside ``[0, R)``, ``state`` is outside ``[0, N)`` (``GRAMMAR_NONE``
+    and ``GRAMMAR_DEAD`` included), ``n_extra[b]`` is outside ``[0, W]``, or the walk meets a
+    token outside ``[0, Vt)`` or a result outside ``[0, N)`` (a forbidden draft)."""
+    B, Vs = logits.shape
+    V = Vs if vocab_size is None else int(vocab_size)
+    dev = logits.device
+    N, Vt = table.shape
+    R = state.shape[0]
+    r = torch.arange(B, device=dev) if rows is None else rows.long()
+    ok = (r >= 0) & (r < R)
+    if active is not None:
+        ok = ok & active.bool()
+    q = state[r.clamp(0, R - 1)].long()
+    ok = ok & (q >= 0) & (q < N)
+    q = q.clamp(0, N - 1)
+    if extra is not None:
+        W = extra.shape[1]
+        ne = n_extra.long()
+        ok = ok & (ne >= 0) & (ne <= W)
+        for j in range(W):
+            step = ok & (j < ne)
+            tok = extra[:, j].long()
+            nx = table[q, tok.clamp(0, Vt - 1)].long()
+            fine = (tok >= 0) & (tok < Vt) & (nx >= 0) & (nx < N)
+            ok = ok & (fine | ~step)
+            q = torch.where(step & fine, nx, q)
+    banned = (table[q][:, :V] < 0) & ok.unsqueeze(1)
+    idt = _BITS[logits.dtype][0]
+    ninf = torch.full((), float("-inf"), dtype=logits.dtype, device=dev).view(idt)
+    raw = logits[:, :V].view(idt)
+    raw.copy_(torch.where(banned, ninf, raw))
+    return logits
+
+
 def _f(x):
     return x.to(torch.promote_types(x.dtype, torch.float32))
 

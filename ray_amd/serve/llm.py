@@ -56,7 +56,21 @@ non-zero ``min_new_tokens`` is an error there). The continuous server needs
 ``build_gpt2_app(..., continuous=True, logit_processors=True)``, which passes the flag to the
 engine; without it a request that names one of the fields gets an error. With
 ``"logprobs"`` the values describe the processed logits, the distribution the token was
-drawn from."""
+drawn from.
+
+Structured output: ``build_gpt2_app(..., grammars={"name": TokenDFA, ...}, eos_token_id=E)``
+(``models/grammar.py``: ``from_choices``, ``from_regex``, ``from_byte_dfa``). A request may
+carry ``"grammar": "name"``, or an inline ``"choices": [[token, ...], ...]`` ("answer with one
+of these"), and its tokens are then a word of that grammar followed by E (a prefix of one where
+``max_new_tokens`` cuts it), whatever its sampling parameters. The static server runs the
+requests of a batch that name a grammar as one ``generate(..., grammar=[...])`` call through
+the device sampler, apart from their batch-mates (which do not end at E), and cuts each result
+after its E. The continuous server also takes ``grammar_states=N``, the rows of the engine's
+pool: the named grammars are registered at start-up, an inline one when its request is
+submitted, and it is dropped when the request ends, is cancelled or fails; a pool without
+room is that request's error. An unknown name, both fields at once, a field the app was not
+built for, and a grammar together with ``min_new_tokens > 0`` or a ``-inf`` ``logit_bias`` are
+each that request's error."""
 
 from __future__ import annotations
 
@@ -125,6 +139,35 @@ def _request_controls(cfg, r, new, eos, enabled=True):
     return kw
 
 
+def _request_grammar(cfg, r, grammars, eos, ctl, new, hint):
+    """The request's grammar as a ``TokenDFA`` (None: it names none): ``"grammar"``, a name of
+    ``grammars``, or inline ``"choices"``; checked against the request's controls ``ctl``.
+    ``grammars`` None: the app was not built for grammars (``hint`` says how)."""
+    from ray_amd.models.gpt2 import checked_controls, checked_grammar
+    from ray_amd.models.grammar import TokenDFA
+
+    name, choices = r.get("grammar"), r.get("choices")
+    if name is None and choices is None:
+        return None
+    if name is not None and choices is not None:
+        raise ValueError("'grammar' and 'choices' are two grammars: pass one")
+    if grammars is None or eos is None:
+        raise ValueError(f"{'grammar' if choices is None else 'choices'!r} needs {hint}")
+    if name is not None:
+        if not isinstance(name, str) or name not in grammars:
+            raise ValueError(f"unknown grammar {name!r}")
+        dfa = grammars[name]
+    else:
+        if not isinstance(choices, list) or \
+                any(not isinstance(c, list) or
+                    any(isinstance(t, bool) or not isinstance(t, int) for t in c)
+                    for c in choices):
+            raise ValueError("choices must be a list of lists of token ids")
+        dfa = TokenDFA.from_choices(choices, cfg.vocab_size, eos)
+    return checked_grammar(dfa, cfg.vocab_size, eos,
+                           checked_controls(cfg.vocab_size, new, eos, **ctl) if ctl else None)
+
+
 def _finite(v):
     return v if v == v and abs(v) != float("inf") else None
 
@@ -139,8 +182,22 @@ def _logprob_fields(lp, ids, tlp, m):
 
 class GPT2Server:
     def __init__(self, config="small", state_dict_path=None, seed=0, max_batch_size=8,
-                 batch_wait_timeout_s=0.01, device=None):
+                 batch_wait_timeout_s=0.01, device=None, grammars=None, eos_token_id=None):
         cfg = getattr(GPT2Config, config)() if isinstance(config, str) else config
+        # grammars: name -> TokenDFA (None: the server answers no grammar request); they,
+        # and inline choices, end with eos_token_id (default: the first grammar's)
+        self.grammars = None if grammars is None and eos_token_id is None else dict(grammars
+                                                                                    or {})
+        if eos_token_id is None and self.grammars:
+            eos_token_id = next(iter(self.grammars.values())).eos_token_id
+        self.eos = eos_token_id
+        for name, dfa in (self.grammars or {}).items():
+            from ray_amd.models.gpt2 import checked_grammar
+
+            try:
+                checked_grammar(dfa, cfg.vocab_size, self.eos)
+            except ValueError as e:
+                raise ValueError(f"grammar {name!r}: {e}") from None
         self.device = _pick_device(device)
         torch.manual_seed(seed)
         model = GPT2(cfg)
@@ -178,11 +235,12 @@ class GPT2Server:
                              "continuous=True, adapters=...)")
         return _request_params(self.model.cfg, self.seed, r)
 
-    def _run_sampled(self, reqs, params, lps=None, ctls=None):
+    def _run_sampled(self, reqs, params, lps=None, ctls=None, grs=None):
         """One ragged generate call through the device sampler, every parameter per row.
         ``lps`` (each request's ``logprobs`` or None; not all None): the call reports the
         batch's widest and every result is a dict cut to its own. ``ctls``: each request's
-        ``_request_controls``."""
+        ``_request_controls``. ``grs``: each request's ``TokenDFA``, none of them None: the
+        call ends rows at the server's EOS and every result is cut after its EOS."""
         lens = [p[0] for p in params]
         new = [p[1] for p in params]
         idx = torch.zeros(len(reqs), max(lens), dtype=torch.long)
@@ -195,12 +253,24 @@ class GPT2Server:
             for k in CONTROL_FIELDS:
                 if any(k in c for c in ctls):
                     kw[k] = [c.get(k) for c in ctls]
+        if grs:
+            kw.update(grammar=grs, eos_token_id=self.eos)
+
+        def cut(out):
+            """``new`` with a grammar row ending after its first EOS."""
+            if not grs:
+                return new
+            rows = [out[b, : new[b]].tolist() for b in range(len(reqs))]
+            return [t.index(self.eos) + 1 if self.eos in t else len(t) for t in rows]
+
         if lps is None or all(m is None for m in lps):
             out = self.model.generate(idx.to(self.device), max(new), **kw).cpu()
+            new = cut(out)
             toks = [out[b, : new[b]].tolist() for b in range(len(reqs))]
             return toks if lps is None else [{"tokens": t} for t in toks]
         out, lp, ids, tlp = (t.cpu() for t in self.model.generate(
             idx.to(self.device), max(new), logprobs=max(m for m in lps if m is not None), **kw))
+        new = cut(out)
         res = []
         for b, m in enumerate(lps):
             res.append({"tokens": out[b, : new[b]].tolist()})
@@ -214,35 +284,45 @@ class GPT2Server:
         from ray_amd.ops.functional import LOGPROB_MAX_TOP
 
         results = [None] * len(reqs)
-        params, lps, ctls = {}, {}, {}
+        params, lps, ctls, grs = {}, {}, {}, {}
         for i, r in enumerate(reqs):
             try:
                 lps[i] = _request_logprobs(r, LOGPROB_MAX_TOP)
                 p = self._params(r)
                 ctls[i] = _request_controls(self.model.cfg, r, p[1], None)
+                grs[i] = _request_grammar(self.model.cfg, r, self.grammars, self.eos, ctls[i],
+                                          p[1], "build_gpt2_app(grammars=..., eos_token_id=...)")
                 params[i] = p
             except Exception as e:  # noqa: BLE001  (one bad request must not fail its batch)
                 results[i] = {"error": f"{type(e).__name__}: {e}"}
         if any(p[2] > 0 or reqs[i].get("top_p") is not None or reqs[i].get("seed") is not None
-               or lps[i] is not None or ctls[i] for i, p in params.items()):
+               or lps[i] is not None or ctls[i] or grs[i] is not None
+               for i, p in params.items()):
             # one call, split only where the longest prompt and the longest continuation
-            # of the batch together would not fit the model's positions
-            chunks, cur = [], []
-            for i in params:
-                trial = cur + [i]
-                if cur and max(params[j][0] for j in trial) + max(params[j][1] for j in trial) \
-                        > self.model.cfg.n_positions:
+            # of the batch together would not fit the model's positions; the requests with a
+            # grammar run apart (their call ends rows at EOS, their batch-mates' does not)
+            chunks = []
+            for constrained in (False, True):
+                cur = []
+                for i in params:
+                    if (grs[i] is not None) != constrained:
+                        continue
+                    trial = cur + [i]
+                    if cur and max(params[j][0] for j in trial) + \
+                            max(params[j][1] for j in trial) > self.model.cfg.n_positions:
+                        chunks.append(cur)
+                        trial = [i]
+                    cur = trial
+                if cur:
                     chunks.append(cur)
-                    trial = [i]
-                cur = trial
-            if cur:
-                chunks.append(cur)
             for members in chunks:
                 try:
                     got = self._run_sampled([reqs[i] for i in members],
                                             [params[i] for i in members],
                                             [lps[i] for i in members],
-                                            [ctls[i] for i in members])
+                                            [ctls[i] for i in members],
+                                            [grs[i] for i in members
+                                             if grs[i] is not None] or None)
                     for i, res in zip(members, got):
                         results[i] = res
                 except ValueError as e:
@@ -313,7 +393,7 @@ class GPT2EngineServer:
     def __init__(self, config="small", state_dict_path=None, seed=0, slots=None,
                  eos_token_id=None, device=None, poll_every=None, prefixes=None,
                  prefill_chunk=None, adapters=None, lora_rank=16, speculate=0, ngram=(2, 4),
-                 logprobs=None, logit_processors=False):
+                 logprobs=None, logit_processors=False, grammars=None, grammar_states=0):
         import queue
         import threading
 
@@ -334,6 +414,12 @@ class GPT2EngineServer:
         self._speculate, self._ngram = speculate, ngram
         self._logprobs = logprobs  # the engine's N (None: it keeps none)
         self._logit_processors = bool(logit_processors)
+        self._grammar_states = int(grammar_states)
+        # grammar name -> TokenDFA (None: the server answers no grammar request)
+        self._grammars = dict(grammars or {}) if self._grammar_states else None
+        if grammars and not self._grammar_states:
+            raise ValueError("grammars need grammar_states=N, the rows of the engine's pool")
+        self._gids = {}  # grammar name -> the engine's grammar id
         self._eos = eos_token_id
         self._pids = {}  # prefix name -> the engine's prefix id
         ready = threading.Event()
@@ -370,7 +456,13 @@ class GPT2EngineServer:
                              prefix_slots=len(self._prefixes),
                              prefill_chunk=self._prefill_chunk, speculate=self._speculate,
                              ngram=self._ngram, logprobs=self._logprobs,
-                             logit_processors=self._logit_processors, **kw)
+                             logit_processors=self._logit_processors,
+                             grammar_states=self._grammar_states, **kw)
+            for name, dfa in (self._grammars or {}).items():
+                try:
+                    self._gids[name] = eng.add_grammar(dfa)
+                except ValueError as e:
+                    raise ValueError(f"grammar {name!r}: {e}") from None
             for i, (name, state) in enumerate(self._adapters.items()):
                 if not isinstance(state, dict):
                     state = torch.load(state, map_location="cpu")
@@ -388,6 +480,13 @@ class GPT2EngineServer:
             ready.set()
         sinks = {}  # engine request id -> (key, loop, asyncio queue)
         rids = {}   # key -> engine request id
+        inline = {}  # engine request id -> the grammar registered for that request alone
+
+        def retire(rid):
+            gid = inline.pop(rid, None)
+            if gid is not None:
+                eng.drop_grammar(gid)
+
         while True:
             msgs = []
             if not eng.has_work():
@@ -405,17 +504,30 @@ class GPT2EngineServer:
                     if rid is not None:
                         eng.cancel(rid)
                         sinks.pop(rid, None)
+                        retire(rid)
                     continue
-                _, key, req, p, ctl, loop, sink = msg
+                _, key, req, p, ctl, dfa, loop, sink = msg
+                gid = None
                 try:
+                    if dfa is not None:
+                        # a named grammar is in the pool; an inline one enters it for the
+                        # time of this request (no room: this request's error)
+                        gid = self._gids.get(req.get("grammar"))
+                        if gid is None:
+                            gid = eng.add_grammar(dfa)
                     rid = eng.submit(req["tokens"], p[1], temperature=p[2], top_k=p[3],
                                      top_p=p[4], seed=p[5],
                                      prefix=self._pids.get(req.get("prefix")),
                                      adapter=self._aids.get(req.get("adapter")),
-                                     logprobs=req.get("logprobs"), **ctl)
+                                     logprobs=req.get("logprobs"),
+                                     **({} if gid is None else {"grammar": gid}), **ctl)
                 except ValueError as e:
+                    if gid is not None and req.get("grammar") is None:
+                        eng.drop_grammar(gid)
                     loop.call_soon_threadsafe(sink.put_nowait, ("error", f"ValueError: {e}"))
                     continue
+                if gid is not None and req.get("grammar") is None:
+                    inline[rid] = gid
                 sinks[rid] = (key, loop, sink)
                 rids[key] = rid
             if not eng.has_work():
@@ -433,6 +545,7 @@ class GPT2EngineServer:
                 if finished:
                     del sinks[rid]
                     rids.pop(key, None)
+                    retire(rid)
                 # (an engine with logprobs: the event's fourth field, None for a request
                 # that asked for none)
                 loop.call_soon_threadsafe(sink.put_nowait,
@@ -454,6 +567,9 @@ class GPT2EngineServer:
             p = _request_params(self.cfg, self.seed, request)
             _request_logprobs(request, self._logprobs)
             ctl = _request_controls(self.cfg, request, p[1], self._eos, self._logit_processors)
+            dfa = _request_grammar(self.cfg, request, self._grammars, self._eos, ctl, p[1],
+                                   "build_gpt2_app(continuous=True, grammar_states=N, "
+                                   "eos_token_id=...)")
             name = request.get("prefix")
             if name is not None and (not isinstance(name, str) or name not in self._pids):
                 raise ValueError(f"unknown prefix {name!r}")
@@ -469,7 +585,7 @@ class GPT2EngineServer:
         key = self._next_key
         self._next_key += 1
         sink = asyncio.Queue()
-        self._inbox.put(("submit", key, request, p, ctl, asyncio.get_running_loop(), sink))
+        self._inbox.put(("submit", key, request, p, ctl, dfa, asyncio.get_running_loop(), sink))
         finished = False
         try:
             while not finished:
@@ -521,7 +637,7 @@ def build_gpt2_app(config="small", state_dict_path=None, seed=0, max_batch_size=
                    batch_wait_timeout_s=0.01, device=None, continuous=False, slots=None,
                    eos_token_id=None, prefixes=None, prefill_chunk=None, adapters=None,
                    lora_rank=16, speculate=0, ngram=(2, 4), logprobs=None,
-                   logit_processors=False):
+                   logit_processors=False, grammars=None, grammar_states=0):
     """A Serve application around one ``GPT2Server`` replica (``serve.run`` it). ``config``
     names a ``GPT2Config`` preset; without ``state_dict_path`` the weights are the seeded
     random init. ``device`` None: the GPU assigned to the replica, else the CPU.
@@ -542,13 +658,21 @@ def build_gpt2_app(config="small", state_dict_path=None, seed=0, max_batch_size=
     needs no option and ignores this one: it answers ``"logprobs": m`` up to 8.
     ``logit_processors=True`` (with ``continuous=True``): the engine keeps the per-slot tables
     of the repetition / presence / frequency penalties, ``logit_bias`` and
-    ``min_new_tokens``, and a request may name them; the static server needs no option."""
+    ``min_new_tokens``, and a request may name them; the static server needs no option.
+    ``grammars={"name": TokenDFA, ...}`` (both servers; they end with ``eos_token_id``, by
+    default the first grammar's on the static server): a request may name one with
+    ``"grammar": "name"`` or carry inline ``"choices"``, and answers with a word of it. The
+    continuous server also needs ``grammar_states=N``, the rows of the engine's pool (about
+    100 KB each at GPT-2's vocabulary): the named grammars' states plus room for the inline
+    grammars of the requests in flight."""
     if continuous:
         dep = deployment(GPT2EngineServer, name="GPT2EngineServer")
         return dep.bind(config, state_dict_path, seed, slots, eos_token_id, device, None,
                         prefixes, prefill_chunk, adapters, lora_rank, speculate, ngram, logprobs,
-                        logit_processors)
-    if prefixes or prefill_chunk is not None or adapters or speculate:
-        raise ValueError("prefixes, prefill_chunk, adapters and speculate need continuous=True")
+                        logit_processors, grammars, grammar_states)
+    if prefixes or prefill_chunk is not None or adapters or speculate or grammar_states:
+        raise ValueError("prefixes, prefill_chunk, adapters, speculate and grammar_states need "
+                         "continuous=True")
     dep = deployment(GPT2Server, name="GPT2Server")
-    return dep.bind(config, state_dict_path, seed, max_batch_size, batch_wait_timeout_s, device)
+    return dep.bind(config, state_dict_path, seed, max_batch_size, batch_wait_timeout_s, device,
+                    grammars, eos_token_id)
