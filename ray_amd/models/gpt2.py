@@ -42,6 +42,10 @@ MI355X-first choices:
   row's automaton state lives on the device, ``rf.grammar_advance`` follows the token just
   emitted and ``rf.grammar_mask`` (ops/csrc/grammar.hip) bans what the state does not allow,
   after the logit processors and before the sampler, inside the captured step as well.
+  Sequence rules (``generate(..., stop=, bad_words=, no_repeat_ngram_size=)``): ``rf.seq_ban``
+  bans the tokens that would complete a banned sequence or repeat an n-gram, between the
+  logit processors and the grammar mask, and ``rf.stop_check`` ends a row whose output just
+  completed a stop sequence (ops/csrc/seq_rules.hip), inside the captured step too.
   The three inference passes (prompt, extend, decode) run ONE layer loop, ``_layers``, and
   hand it their attention step; the training ``forward`` keeps its own (autograd ops).
 """
@@ -186,7 +190,7 @@ class _SeededSampler:
     and a token then costs one replay."""
 
     def __init__(self, model, cache, logits, out, temperature, top_k, top_p, seeds, eos,
-                 adapters=None, logprobs=None, controls=None, grammar=None):
+                 adapters=None, logprobs=None, controls=None, grammar=None, rules=None):
         cfg = model.cfg
         dev = out.device
         B = out.shape[0]
@@ -211,10 +215,17 @@ class _SeededSampler:
         # sampler reads it (rf.logit_process on the prefill's here, on decode_step's in _step);
         # n_out counts the tokens in ``out``, advanced where ``col`` is (None: no such call)
         self.ctl = controls
-        if controls is not None or grammar is not None:
+        if controls is not None or grammar is not None or rules is not None:
             self.n_out = torch.zeros(B, dtype=torch.int32, device=dev)
         if controls is not None:
             self.ctl.process(self.logits, self.out, self.n_out, self.eos)
+        # rules=SequenceRules: the buffer holds logits with the banned sequences' and repeated
+        # n-grams' tokens at -inf whenever the sampler reads it (rf.seq_ban after the logit
+        # processors, before the grammar mask), and rf.stop_check latches ``done`` for a row
+        # whose output just completed a stop sequence (None: no such call)
+        self.rules = rules
+        if rules is not None:
+            rules.ban(self.logits, self.out, self.n_out)
         # grammar=(table int16 [N, Vt], start states int32 [B]): each row's automaton state and
         # the number of tokens of ``out`` it has consumed; the buffer holds MASKED logits
         # whenever the sampler reads it (None: no such call)
@@ -244,12 +255,17 @@ class _SeededSampler:
         if self.lp is not None:
             self.cols += 1
         self.model.decode_step(self.tok, self.cache, out=self.buf, adapters=self.adapters)
-        if self.ctl is not None or self.gtable is not None:
+        if self.ctl is not None or self.gtable is not None or self.rules is not None:
             self.n_out += 1  # ``out`` already holds the token just drawn
+        if self.rules is not None:
+            # a stopped row is padded with EOS from here on, as a row that drew EOS is
+            self.rules.check(self.out, self.n_out, done=self.done, max_span=1)
         if self.gtable is not None:
             rf.grammar_advance(self.gstate, self.gpos, self.out, self.n_out, self.gtable, 1)
         if self.ctl is not None:
             self.ctl.process(self.logits, self.out, self.n_out, self.eos)
+        if self.rules is not None:
+            self.rules.ban(self.logits, self.out, self.n_out)
         if self.gtable is not None:
             rf.grammar_mask(self.logits, self.gtable, self.gstate)
 
@@ -400,6 +416,146 @@ def checked_grammar(dfa, vocab_size, eos_token_id, controls=None):
             raise ValueError("grammar and a -inf logit_bias cannot go together: no allowed "
                              "token might be left")
     return dfa
+
+
+def checked_sequences(vocab_size, eos_token_id, stop=None, bad_words=None,
+                      no_repeat_ngram_size=None):
+    """One request's sequence rules, checked: ``(stops, bads, n)``, two lists of token lists
+    and the no-repeat n-gram size (0: off), or None when none of the three is given. A bare
+    int in ``stop`` or ``bad_words`` counts as a one-token sequence. ``ValueError`` for more
+    than ``rf.SEQ_MAX`` sequences of one kind, an empty sequence or one longer than
+    ``rf.SEQ_MAX_LEN``, an id outside ``[0, vocab_size)``, ``no_repeat_ngram_size`` outside
+    ``0..rf.SEQ_MAX_LEN``, a bool or a non-int where an int belongs, and ``stop`` without
+    ``eos_token_id`` (a stopped row of ``generate`` is padded with it)."""
+    if stop is None and bad_words is None and no_repeat_ngram_size is None:
+        return None
+
+    def is_int(v):
+        return isinstance(v, int) and not isinstance(v, bool)
+
+    def sequences(name, value):
+        if value is None:
+            return []
+        if not isinstance(value, (list, tuple)):
+            raise ValueError(f"{name} must be a list of token sequences, got {value!r}")
+        if len(value) > rf.SEQ_MAX:
+            raise ValueError(f"{name} has {len(value)} sequences, at most {rf.SEQ_MAX} fit")
+        res = []
+        for seq in value:
+            seq = [seq] if is_int(seq) else seq
+            if not isinstance(seq, (list, tuple)) or not 1 <= len(seq) <= rf.SEQ_MAX_LEN:
+                raise ValueError(f"a {name} sequence must hold 1..{rf.SEQ_MAX_LEN} tokens, got "
+                                 f"{seq!r}")
+            if any(not is_int(t) or not 0 <= t < vocab_size for t in seq):
+                raise ValueError(f"{name} ids must be ints in [0, {vocab_size}), got {seq!r}")
+            res.append(list(seq))
+        return res
+
+    stops, bads = sequences("stop", stop), sequences("bad_words", bad_words)
+    if stops and eos_token_id is None:
+        raise ValueError("stop needs eos_token_id")
+    n = 0 if no_repeat_ngram_size is None else no_repeat_ngram_size
+    if not is_int(n) or not 0 <= n <= rf.SEQ_MAX_LEN:
+        raise ValueError(f"no_repeat_ngram_size must be an int in 0..{rf.SEQ_MAX_LEN}, got "
+                         f"{no_repeat_ngram_size!r}")
+    return stops, bads, n
+
+
+def checked_grammar_sequences(dfa, rules):
+    """The check beside ``checked_grammar`` for a request with a grammar and a
+    ``checked_sequences`` result: ``ValueError`` for ``bad_words`` or ``no_repeat_ngram_size >
+    0``, either of which could leave a row with no allowed token. ``stop`` goes with a grammar:
+    the output is then a prefix of a word, as at ``max_new_tokens``."""
+    if dfa is None or rules is None:
+        return
+    if rules[1]:
+        raise ValueError("grammar and bad_words cannot go together: no allowed token might be "
+                         "left")
+    if rules[2] > 0:
+        raise ValueError("grammar and no_repeat_ngram_size > 0 cannot go together: no allowed "
+                         "token might be left")
+
+
+class SequenceRules:
+    """The per-row tables of ``rf.seq_ban`` and ``rf.stop_check`` for R rows, at fixed
+    addresses: ``stops`` / ``bad`` int32 [R, SEQ_MAX, SEQ_MAX_LEN] with ``stop_len`` /
+    ``bad_len`` int32 [R, SEQ_MAX], ``ngram`` int32 [R] (all unused until ``put``), ``pos``
+    int32 [R] (the output tokens ``check`` has looked at) and ``hit`` int32 [R] (the stop
+    sequence that ended the row, -1: none), and the prompts int32 [R, width]. ``controls``: a
+    ``LogitControls`` of the same R and width whose prompt table is then shared, one copy:
+    its ``put`` writes the prompts, this one's does not."""
+
+    def __init__(self, R, width, device, controls=None):
+        i32, Q, ML = torch.int32, rf.SEQ_MAX, rf.SEQ_MAX_LEN
+        self.stops = torch.zeros(R, Q, ML, dtype=i32, device=device)
+        self.stop_len = torch.zeros(R, Q, dtype=i32, device=device)
+        self.bad = torch.zeros(R, Q, ML, dtype=i32, device=device)
+        self.bad_len = torch.zeros(R, Q, dtype=i32, device=device)
+        self.ngram = torch.zeros(R, dtype=i32, device=device)
+        self.pos = torch.zeros(R, dtype=i32, device=device)
+        self.hit = torch.full((R,), -1, dtype=i32, device=device)
+        self.shared = controls is not None
+        if self.shared:
+            if controls.prompt.shape != (R, width):
+                raise ValueError("the shared prompt table has another shape")
+            self.prompt, self.prompt_len = controls.prompt, controls.prompt_len
+        else:
+            self.prompt = torch.zeros(R, width, dtype=i32, device=device)
+            self.prompt_len = torch.zeros(R, dtype=i32, device=device)
+
+    def put(self, rows, rules, prompts):
+        """Writes rows ``rows`` (int64 [n] on the device): ``rules[i]`` a ``checked_sequences``
+        result (None: no rule), ``prompts[i]`` the row's prompt tokens; ``pos`` becomes 0 and
+        ``hit`` -1. One upload, however many rows."""
+        n, Q, ML = len(rules), rf.SEQ_MAX, rf.SEQ_MAX_LEN
+        width = 0 if self.shared else self.prompt.shape[1]
+        o_len, o_seq, o_p = 2, 2 + 2 * Q, 2 + 2 * Q + 2 * Q * ML
+        ints = torch.zeros(n, o_p + width, dtype=torch.int32)
+        for i, (r, p) in enumerate(zip(rules, prompts)):
+            stops, bads, ng = r if r is not None else ([], [], 0)
+            ints[i, 0], ints[i, 1] = ng, len(p)
+            for k, seqs in enumerate((stops, bads)):
+                for q, seq in enumerate(seqs):
+                    ints[i, o_len + k * Q + q] = len(seq)
+                    at = o_seq + (k * Q + q) * ML
+                    ints[i, at: at + len(seq)] = torch.tensor(seq, dtype=torch.int32)
+            if width:
+                ints[i, o_p: o_p + len(p)] = torch.as_tensor(p, dtype=torch.int32)
+        ints = ints.to(rows.device)
+        seqs = ints[:, o_seq: o_p].view(n, 2, Q, ML)
+        for dst, src in ((self.ngram, ints[:, 0]), (self.stop_len, ints[:, o_len: o_len + Q]),
+                         (self.bad_len, ints[:, o_len + Q: o_seq]), (self.stops, seqs[:, 0]),
+                         (self.bad, seqs[:, 1])):
+            dst.index_copy_(0, rows, src)
+        if width:
+            self.prompt_len.index_copy_(0, rows, ints[:, 1])
+            self.prompt.index_copy_(0, rows, ints[:, o_p:])
+        self.pos.index_fill_(0, rows, 0)
+        self.hit.index_fill_(0, rows, -1)
+
+    def ban(self, logits, out, n_out, **kw):
+        """``rf.seq_ban`` on ``logits`` with these tables."""
+        return rf.seq_ban(logits, self.prompt, self.prompt_len, out, n_out, self.bad,
+                          self.bad_len, self.ngram, **kw)
+
+    def check(self, out, n_out, **kw):
+        """``rf.stop_check`` on ``out`` / ``n_out`` with these tables."""
+        return rf.stop_check(out, n_out, self.pos, self.stops, self.stop_len, self.hit, **kw)
+
+
+def _per_row_sequences(name, value, B):
+    """``generate``'s ``stop`` / ``bad_words`` as a list of B values. One value for all rows
+    is a list of sequences (token lists or bare ints); the per-row form is a list of B entries,
+    each None or such a list, recognised by an entry that is None or that holds a list."""
+    if value is None:
+        return [None] * B
+    if isinstance(value, (list, tuple)) and any(
+            v is None or (isinstance(v, (list, tuple)) and
+                          any(isinstance(t, (list, tuple)) for t in v)) for v in value):
+        if len(value) != B:
+            raise ValueError(f"{name} has {len(value)} entries for {B} rows")
+        return list(value)
+    return [value] * B
 
 
 def grammar_table(dfas):
@@ -743,7 +899,8 @@ class GPT2(nn.Module):
     def generate(self, idx, max_new_tokens, *, lens=None, temperature=0.0, top_k=None,
                  top_p=None, seeds=None, eos_token_id=None, generator=None, graph=False,
                  adapters=None, logprobs=None, repetition_penalty=None, presence_penalty=None,
-                 frequency_penalty=None, min_new_tokens=None, logit_bias=None, grammar=None):
+                 frequency_penalty=None, min_new_tokens=None, logit_bias=None, grammar=None,
+                 stop=None, bad_words=None, no_repeat_ngram_size=None):
         """Autoregressive generation with a KV cache: ``idx`` [B, T] prompts, right-padded
         to a common length with true lengths ``lens`` (default: all T). Returns the new
         tokens [B, max_new_tokens] (int64). ``temperature`` 0 is greedy, otherwise samples
@@ -795,7 +952,24 @@ class GPT2(nn.Module):
         captured step: a token still costs one replay, and ``logprobs=`` reports the masked
         distribution. ``min_new_tokens > 0`` or a ``-inf`` ``logit_bias`` on a row with a
         grammar is a ``ValueError`` (either could leave no token). Without ``grammar`` not
-        one extra op runs."""
+        one extra op runs.
+
+        Sequence rules (they need ``seeds=``; ``stop`` and ``bad_words`` are one list of token
+        sequences for all rows, a bare int counting as a one-token sequence, or a list with
+        one entry per row, each None or such a list, recognised by an entry that is None or
+        holds a list; ``no_repeat_ngram_size`` is an int or one per row): ``stop`` (needs
+        ``eos_token_id``) ends a row right after the first of its sequences that the output
+        completes, and the row is padded with EOS from there as after EOS itself;
+        ``bad_words`` never lets the output, or the prompt followed by the output, complete one
+        of its sequences; ``no_repeat_ngram_size=n`` (1..``rf.SEQ_MAX_LEN``; 0: off) never lets
+        an n-gram occur twice in prompt plus output (the Hugging Face rule). At most
+        ``rf.SEQ_MAX`` sequences of a kind with at most ``rf.SEQ_MAX_LEN`` tokens each.
+        ``rf.seq_ban`` sets the banned tokens' logits to ``-inf`` after the logit processors
+        and before the grammar mask, ``rf.stop_check`` follows the token just written
+        (ops/csrc/seq_rules.hip), both on the device and inside the captured step: a row's
+        tokens depend on that row alone and a token still costs one replay. ``logprobs=``
+        reports the banned distribution. A grammar goes with ``stop`` only. With none of
+        the three given not one extra op runs."""
         cfg = self.cfg
         B, T = idx.shape
         if logprobs is not None:
@@ -806,10 +980,13 @@ class GPT2(nn.Module):
                                    ("frequency_penalty", frequency_penalty),
                                    ("min_new_tokens", min_new_tokens),
                                    ("logit_bias", logit_bias)) if v is not None}
+        seq_named = {k: v for k, v in (("stop", stop), ("bad_words", bad_words),
+                                       ("no_repeat_ngram_size", no_repeat_ngram_size))
+                     if v is not None}
         if seeds is None:
             if top_p is not None:
                 raise ValueError("top_p needs the device sampler: pass seeds=")
-            for k in named:
+            for k in list(named) + list(seq_named):
                 raise ValueError(f"{k} needs the device sampler: pass seeds=")
             if grammar is not None:
                 raise ValueError("grammar needs the device sampler: pass seeds=")
@@ -856,6 +1033,13 @@ class GPT2(nn.Module):
             idx_l = idx.tolist()
             ctl.put(torch.arange(B, device=dev), rows_c,
                     [idx_l[b][: lens_l[b]] for b in range(B)])
+        rows_s = None
+        if seq_named:
+            stops = _per_row_sequences("stop", stop, B)
+            bads = _per_row_sequences("bad_words", bad_words, B)
+            ngs = _per_row("no_repeat_ngram_size", no_repeat_ngram_size, None, B, lambda x: x)
+            rows_s = [checked_sequences(cfg.vocab_size, eos_token_id, stops[b], bads[b], ngs[b])
+                      for b in range(B)]
         gram = None
         if grammar is not None:
             per_row = _per_row("grammar", grammar, None, B, lambda x: x)
@@ -865,12 +1049,20 @@ class GPT2(nn.Module):
                     dfas.append(checked_grammar(d, cfg.vocab_size, eos_token_id))
                 if d is not None and rows_c is not None:
                     checked_grammar(d, cfg.vocab_size, eos_token_id, rows_c[b])
+                if rows_s is not None:
+                    checked_grammar_sequences(d, rows_s[b])
             if dfas:
                 table, offs = grammar_table(dfas)
                 first = {id(d): o + d.start for d, o in zip(dfas, offs)}
                 start = [rf.GRAMMAR_NONE if d is None else first[id(d)] for d in per_row]
                 gram = (torch.from_numpy(table).to(dev),
                         torch.tensor(start, dtype=torch.int32, device=dev))
+        rules = None
+        if rows_s is not None and any(r is not None for r in rows_s):
+            rules = SequenceRules(B, T, dev, controls=ctl)
+            idx_l = idx.tolist()
+            rules.put(torch.arange(B, device=dev), rows_s,
+                      [idx_l[b][: lens_l[b]] for b in range(B)])
         cache = KVCache(cfg, B, max(lens_l) + max_new_tokens, dev, self.wte.dtype)
         logits = self.prefill(idx, torch.tensor(lens_l, dtype=torch.int32, device=dev), cache,
                               adapters=ad)
@@ -878,7 +1070,7 @@ class GPT2(nn.Module):
         if seeds is not None:
             eos = None if eos_token_id is None else int(eos_token_id)
             step = _SeededSampler(self, cache, logits, out, temps, ks, ps, seeds_l, eos, ad,
-                                  logprobs, ctl, gram)
+                                  logprobs, ctl, gram, rules)
             res = out if logprobs is None else (out,) + step.lp
             if max_new_tokens > 1:
                 step()

@@ -136,6 +136,33 @@ controls>)`` on it alone, with prefixes, chunked prefill, adapters, ``cancel``, 
 logit processors and every ``speculate``; a request without a grammar gets the tokens it got
 before, whoever shares the step.
 
+Sequence rules (``sequence_rules=True``; False, the default, is the engine without them: no
+buffer, no extra op, and ``submit`` rejects the fields): ``submit(..., stop=, bad_words=,
+no_repeat_ngram_size=)`` as in ``generate``, one request's value each. The tables
+(``SequenceRules``: the stop and banned sequences with their lengths, the n-gram size, ``pos``
+and ``hit`` per slot, and the prompts, ONE copy shared with the logit processors' when both
+exist) sit at fixed addresses and are written when a slot's prompt is complete, the prefix's
+tokens included, with ``pos = 0`` and ``hit = -1``; ``rf.seq_ban`` then edits that round's
+prefill rows, after the logit processors and before the grammar mask, before they go into
+``self.buf``. The invariant: ``self.buf`` holds rows with the banned tokens at ``-inf``. The
+plain step runs ``rf.stop_check`` right after ``rf.slot_advance`` with ``active`` and
+``cache.lens``, so a slot whose output just completed a stop sequence is an inactive row for
+``decode_step`` already, and ``rf.seq_ban`` at its end between the logit processors and
+``rf.grammar_mask``. The speculative step bans on the window's logits with the ``rows`` /
+``extra`` / ``n_extra`` / ``live`` construction of the logit processors (row j sees exactly
+the tokens before its position) and runs ``rf.stop_check`` with ``max_span = k + 1`` right
+after ``rf.spec_accept``: it cuts ``n_out`` back to the first completed stop inside the
+accepted window, also when ``spec_accept`` has already retired the slot at a later EOS or at
+``max_new_tokens`` (``stop_check`` never reads ``active``). What lies beyond the cut in ``out``,
+``hist`` and the logprob tables is never read. ``hit`` names the stop sequence that ended a
+slot's request (-1: none); events keep their shape. A request's tokens, and its logprobs,
+are those of ``generate(..., seeds=[seed], <same rules>)`` on it alone, cut after the first
+EOS or the first completed stop sequence, whichever ends earlier, with prefixes, chunked
+prefill, adapters, ``cancel``, logit processors, grammars (``stop`` only: ``bad_words`` or
+``no_repeat_ngram_size > 0`` with a grammar is a ``ValueError``), ``logprobs`` and every
+``speculate``; a request that names no rule gets the tokens it got before, whoever shares
+the step.
+
 Single-threaded by contract: every call comes from one thread."""
 
 from __future__ import annotations
@@ -146,8 +173,9 @@ import math
 import numpy as np
 import torch
 
-from ray_amd.models.gpt2 import (GPT2, KVCache, LogitControls, checked_controls,
-                                 checked_grammar)
+from ray_amd.models.gpt2 import (GPT2, KVCache, LogitControls, SequenceRules, checked_controls,
+                                 checked_grammar, checked_grammar_sequences,
+                                 checked_sequences)
 from ray_amd.models.grammar import MAX_STATES, padded_vocab
 from ray_amd.ops import functional as rf
 from ray_amd.ops.graph_lock import CapturedStep
@@ -155,10 +183,10 @@ from ray_amd.ops.graph_lock import CapturedStep
 
 class _Request:
     __slots__ = ("rid", "tokens", "max_new", "temperature", "top_k", "top_p", "seed", "pid",
-                 "adapter", "logprobs", "controls", "grammar")
+                 "adapter", "logprobs", "controls", "grammar", "rules")
 
     def __init__(self, rid, tokens, max_new, temperature, top_k, top_p, seed, pid=None,
-                 adapter=-1, logprobs=None, controls=None, grammar=None):
+                 adapter=-1, logprobs=None, controls=None, grammar=None, rules=None):
         # tokens: the whole prompt (the prefix's tokens included); pid: the prefix it names
         self.rid, self.tokens, self.max_new = rid, tokens, max_new
         self.temperature, self.top_k, self.top_p, self.seed = temperature, top_k, top_p, seed
@@ -167,13 +195,14 @@ class _Request:
         self.logprobs = logprobs  # None: the request reports none; else its top-n width
         self.controls = controls  # a checked_controls result (None: neutral)
         self.grammar = grammar  # an add_grammar id (None: unconstrained)
+        self.rules = rules  # a checked_sequences result (None: no rule)
 
 
 class GPT2Engine:
     def __init__(self, model: GPT2, slots=8, max_len=None, eos_token_id=None, graph=None,
                  poll_every=8, prefix_slots=0, prefill_chunk=None, lora=None, speculate=0,
                  ngram=(2, 4), drafter=None, logprobs=None, logit_processors=False,
-                 grammar_states=0):
+                 grammar_states=0, sequence_rules=False):
         cfg = model.cfg
         dev = model.wte.device
         S = int(slots)
@@ -297,6 +326,18 @@ class GPT2Engine:
                 self._g_n_extra = torch.arange(1, W + 1, dtype=torch.int32, device=dev).repeat(S)
         self._has_grammar = bool(grammar_states)
 
+        self._has_seq = bool(sequence_rules)
+        if sequence_rules:
+            # the slots' sequence tables: fixed addresses, rewritten in place (_fill_rows); the
+            # prompts are the logit processors' copy where there is one
+            self.seq = SequenceRules(S, self.max_len, dev, controls=self.ctl)
+            if speculate:
+                W = speculate + 1
+                self._seq_rows = self.cache.rows.repeat_interleave(W)
+                self._seq_idx = torch.arange(W, dtype=torch.int32, device=dev).unsqueeze(0)
+                self._seq_n_extra = torch.arange(1, W + 1, dtype=torch.int32,
+                                                 device=dev).repeat(S)
+
         self._queue = collections.deque()
         self._slot_req = [None] * S  # the request running in each slot
         self._seen_host = [0] * S
@@ -330,6 +371,11 @@ class GPT2Engine:
                               rows=self.cache.rows, cols=self.n_out, active=self.active)
         rf.slot_advance(tok, self.cache.lens, self.n_out, self.max_new, self.active, self.out,
                         self.eos)
+        if self._has_seq:
+            # the token just stored may complete a stop sequence: the slot is then inactive
+            # for decode_step already
+            self.seq.check(self.out, self.n_out, active=self.active, lens=self.cache.lens,
+                           max_span=1)
         self.model.decode_step(tok, self.cache, out=self.buf, adapters=self.adapter)
         if self._has_grammar:
             # the state follows tok (a slot without a grammar, or one that is idle and has
@@ -338,6 +384,8 @@ class GPT2Engine:
         if self.ctl is not None:
             # out / n_out hold tok, and a slot that just finished is inactive
             self.ctl.process(self.logits, self.out, self.n_out, self.eos, active=self.active)
+        if self._has_seq:
+            self.seq.ban(self.logits, self.out, self.n_out, active=self.active)
         if self._has_grammar:
             rf.grammar_mask(self.logits, self.gtable, self.gstate, active=self.active)
 
@@ -362,6 +410,13 @@ class GPT2Engine:
                              extra=win.unsqueeze(1).expand(S, W, W).reshape(S * W, W),
                              n_extra=self._ctl_n_extra,
                              active=live.to(torch.uint8).view(S * W))
+        if self._has_seq:
+            # window row j, as for the logit processors: its context ends with win[s, :j + 1]
+            live = (self._seq_idx < n_win.unsqueeze(1)) & self.active.bool().unsqueeze(1)
+            self.seq.ban(self.logits_win.view(S * W, -1)[:, :V], self.out, self.n_out,
+                         rows=self._seq_rows,
+                         extra=win.unsqueeze(1).expand(S, W, W).reshape(S * W, W),
+                         n_extra=self._seq_n_extra, active=live.to(torch.uint8).view(S * W))
         if self._has_grammar:
             # window row j: the slot's state walked over win[s, :j + 1]; a forbidden draft
             # leaves its row and the later ones unmasked, and is rejected by the row before
@@ -390,12 +445,18 @@ class GPT2Engine:
         rf.spec_accept(win, n_win, cand.view(S, W), self.logits_win, lens, self.n_out,
                        self.max_new, self.active, self.out, self.hist, self.buf, self.n_drafted,
                        self.n_accepted, self.eos)
+        if self._has_seq:
+            # the first stop sequence completed inside the kept tokens cuts n_out back to its
+            # end, also in a slot that spec_accept just retired at a later EOS or at max_new
+            self.seq.check(self.out, self.n_out, active=self.active, lens=lens, max_span=W)
         if self._has_grammar:
             rf.grammar_advance(self.gstate, self.gpos, self.out, self.n_out, self.gtable, W)
 
     def spec_stats(self):
         """``{"drafted": n, "accepted": m}``: the draft tokens the verify passes checked so
-        far and the ones that became output, over all requests. One download."""
+        far and the ones that became output, over all requests. One download. With
+        ``sequence_rules=True`` these keep counting what the sampler accepted: a draft that was
+        accepted and then cut off by a stop sequence still counts as accepted."""
         if not self.speculate:
             return {"drafted": 0, "accepted": 0}
         n, m = torch.stack([self.n_drafted.sum(), self.n_accepted.sum()]).tolist()
@@ -547,7 +608,8 @@ class GPT2Engine:
     def submit(self, tokens, max_new_tokens, temperature=0.0, top_k=None, top_p=None, seed=0,
                prefix=None, adapter=None, logprobs=None, repetition_penalty=None,
                presence_penalty=None, frequency_penalty=None, logit_bias=None,
-               min_new_tokens=None, grammar=None):
+               min_new_tokens=None, grammar=None, stop=None, bad_words=None,
+               no_repeat_ngram_size=None):
         """Queues a request and returns its id; a bad request raises ``ValueError`` and
         queues nothing. ``prefix``: an ``add_prefix`` id; ``tokens`` is then the non-empty
         continuation and the request's prompt is the prefix's tokens followed by it.
@@ -560,7 +622,10 @@ class GPT2Engine:
         in ``generate``, on an engine built with ``logit_processors=True``. ``grammar``: an
         ``add_grammar`` id on an engine built with ``grammar_states=N``: the output is a word
         of that grammar; not together with ``min_new_tokens > 0`` or a ``-inf``
-        ``logit_bias``."""
+        ``logit_bias``. ``stop``, ``bad_words`` (lists of token sequences, a bare int counting
+        as one token) and ``no_repeat_ngram_size``: as in ``generate``, on an engine built with
+        ``sequence_rules=True``; ``stop`` needs the engine's ``eos_token_id``, and a grammar
+        goes with ``stop`` only."""
         tokens = self._checked_tokens(tokens, "request")
         if grammar is not None:
             self._need_pool("grammar given")
@@ -575,6 +640,12 @@ class GPT2Engine:
             if v is not None and self.ctl is None:
                 raise ValueError(f"{k} given, but the engine has no logit processors: "
                                  "logit_processors=True")
+        rules = {"stop": stop, "bad_words": bad_words,
+                 "no_repeat_ngram_size": no_repeat_ngram_size}
+        for k, v in rules.items():
+            if v is not None and not self._has_seq:
+                raise ValueError(f"{k} given, but the engine has no sequence rules: "
+                                 "sequence_rules=True")
         if logprobs is not None:
             if self.logprobs is None:
                 raise ValueError("logprobs given, but the engine keeps none: logprobs=")
@@ -612,13 +683,15 @@ class GPT2Engine:
             seed -= 2 ** 64
         top_k = max(0, min(top_k, 2 ** 31 - 1))
         controls = checked_controls(self.model.cfg.vocab_size, max_new, self.eos, **controls)
+        rules = checked_sequences(self.model.cfg.vocab_size, self.eos, **rules)
         if grammar is not None:  # the combinations that could leave a row no token
             checked_grammar(self._grammars[grammar][3], self.model.cfg.vocab_size, self.eos,
                             controls)
+            checked_grammar_sequences(self._grammars[grammar][3], rules)
         rid = self._next_rid
         self._next_rid += 1
         self._queue.append(_Request(rid, tokens, max_new, temperature, top_k, top_p, seed,
-                                    prefix, adapter, logprobs, controls, grammar))
+                                    prefix, adapter, logprobs, controls, grammar, rules))
         return rid
 
     def cancel(self, rid):
@@ -730,6 +803,11 @@ class GPT2Engine:
             # round's rows: self.buf only ever holds processed logits
             self.ctl.put(sl, [reqs[j].controls for j in done], [reqs[j].tokens for j in done])
             self.ctl.process(logits, self.out, self.n_out, self.eos, rows=sl.to(torch.int32))
+        if self._has_seq:
+            # the slots' rules (pos = 0, hit = -1; the prompts too unless the logit processors'
+            # copy is shared), then this round's rows: self.buf only ever holds banned logits
+            self.seq.put(sl, [reqs[j].rules for j in done], [reqs[j].tokens for j in done])
+            self.seq.ban(logits, self.out, self.n_out, rows=sl.to(torch.int32))
         if self._has_grammar:
             # the slots' start states (GRAMMAR_NONE without a grammar), then this round's
             # rows: self.buf only ever holds masked logits

@@ -144,6 +144,10 @@ _SIGS = {
     "ra_grammar_mask_chunk": [c_int, c_int],
     "ra_grammar_mask": [c_void_p, c_long] + [c_void_p] * 6 + [c_int] * 7 + [c_void_p],
     "ra_grammar_advance": [c_void_p] * 5 + [c_int] * 5 + [c_void_p],
+    "ra_seq_max": [],
+    "ra_seq_max_len": [],
+    "ra_seq_ban": [c_void_p, c_long] + [c_void_p] * 11 + [c_int] * 6 + [c_void_p],
+    "ra_stop_check": [c_void_p] * 9 + [c_int] * 3 + [c_void_p],
     "ra_gemm_nt": [c_void_p, c_long, c_void_p, c_long, c_void_p, c_long, c_int, c_int, c_int,
                    c_int, c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_int, c_int,
                    c_void_p],

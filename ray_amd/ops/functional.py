@@ -1395,6 +1395,146 @@ def grammar_mask(logits, table, state, rows=None, extra=None, n_extra=None, acti
     return logits
 
 
+SEQ_MAX = ref.SEQ_MAX          # ops/csrc/seq_rules.hip kSeqMax (checked against the library, once)
+SEQ_MAX_LEN = ref.SEQ_MAX_LEN  # kSeqMaxLen there; no_repeat_ngram_size is in 0..SEQ_MAX_LEN
+_seq_lib = None
+
+
+def _seq_library():
+    """The library, its sequence limits checked against this module's the first time."""
+    global _seq_lib
+    if _seq_lib is None:
+        L = _lib.lib()
+        assert L.ra_seq_max() == SEQ_MAX
+        assert L.ra_seq_max_len() == SEQ_MAX_LEN
+        _seq_lib = L
+    return _seq_lib
+
+
+def _seq_tables(op, names, seqs, seq_len, R, like):
+    _table(names[0], op, seqs, (R, SEQ_MAX, SEQ_MAX_LEN), like, torch.int32)
+    _table(names[1], op, seq_len, (R, SEQ_MAX), like, torch.int32)
+
+
+def seq_ban(logits, prompt, prompt_len, out, n_out, bad, bad_len, ngram, rows=None, extra=None,
+            n_extra=None, active=None, vocab_size=None):
+    """Banned token sequences and no-repeat n-grams, applied IN PLACE to the rows of ``logits``
+    [B, Vs] (the first ``vocab_size or Vs`` columns count) as a function of each row's own
+    token history. Semantics: ``reference.seq_ban``, bit for bit. Returns ``logits``.
+
+    The context of logits row b is row ``rows[b]`` (int32 [B], default b) of ``prompt`` int32
+    [R, P] / ``prompt_len`` int32 [R] and ``out`` int64 [R, cap] / ``n_out`` int32 [R], then
+    ``extra[b, :n_extra[b]]`` (int64 [B, W], int32 [B]); its rules are ``bad`` int32 [R,
+    ``SEQ_MAX``, ``SEQ_MAX_LEN``] with ``bad_len`` int32 [R, ``SEQ_MAX``] (0: unused) and
+    ``ngram`` int32 [R] (0: off). The last token of a banned sequence whose other tokens end
+    the context, and every token that would complete an n-gram the context already holds,
+    becomes ``-inf``. A row with ``active[b] == 0`` (uint8 [B]), a context row or a length out
+    of range, ``ngram`` outside ``0..SEQ_MAX_LEN`` or no rule keeps its bytes; so does every
+    element that no rule names.
+
+    HIP kernel (ops/csrc/seq_rules.hip: one launch, one workgroup per row, every index read
+    and checked on the device, no host sync, capturable; it writes the banned elements only)
+    for GPU tensors with bf16 logits of unit column stride and at most ``SAMPLE_MAX_VOCAB``
+    columns; the rows may be a column slice of a wider buffer, edited in place. CPU tensors,
+    other dtypes and wider vocabularies use the plain-torch reference."""
+    op = "seq_ban"
+    if not isinstance(logits, torch.Tensor) or logits.dim() != 2:
+        raise ValueError(f"{op}: logits must be [B, V]")
+    B, Vs = logits.shape
+    V = Vs if vocab_size is None else int(vocab_size)
+    if B < 1 or V < 1 or V > Vs:
+        raise ValueError(f"{op}: vocab_size {V} does not fit logits {tuple(logits.shape)}")
+    if logits.dtype not in ref._BITS:
+        raise ValueError(f"{op}: logits must be floating point")
+    if not isinstance(prompt, torch.Tensor) or prompt.dim() != 2 or prompt.shape[0] < 1:
+        raise ValueError(f"{op}: prompt must be an int32 tensor [R, P]")
+    R, P = prompt.shape
+    _table("prompt", op, prompt, (R, P), logits, torch.int32)
+    if not isinstance(out, torch.Tensor) or out.dim() != 2:
+        raise ValueError(f"{op}: out must be an int64 tensor [R, cap]")
+    cap = out.shape[1]
+    _table("out", op, out, (R, cap), logits, torch.int64)
+    _seq_tables(op, ("bad", "bad_len"), bad, bad_len, R, logits)
+    for name, t in (("prompt_len", prompt_len), ("n_out", n_out), ("ngram", ngram)):
+        _int_vec(name, op, t, R, logits)
+    if rows is None:
+        if R < B:
+            raise ValueError(f"{op}: {B} logits rows need rows= to share {R} context rows")
+    else:
+        _int_vec("rows", op, rows, B, logits)
+    W = 0
+    if (extra is None) != (n_extra is None):
+        raise ValueError(f"{op}: extra and n_extra go together")
+    if extra is not None:
+        if not isinstance(extra, torch.Tensor) or extra.dim() != 2:
+            raise ValueError(f"{op}: extra must be an int64 tensor [B, W]")
+        W = extra.shape[1]
+        _table("extra", op, extra, (B, W), logits, torch.int64)
+        _int_vec("n_extra", op, n_extra, B, logits)
+    if active is not None:
+        _int_vec("active", op, active, B, logits, torch.uint8)
+    hip = _hip(logits) and logits.dtype == torch.bfloat16 and V <= SAMPLE_MAX_VOCAB and \
+        logits.stride(1) == 1 and (B == 1 or logits.stride(0) >= V) and \
+        (extra is None or W > 0)
+    if not hip:
+        return ref.seq_ban(logits, prompt, prompt_len, out, n_out, bad, bad_len, ngram, rows,
+                           extra, n_extra, active, V)
+    L = _seq_library()
+    c = torch.Tensor.contiguous
+    check(L.ra_seq_ban(
+        ptr(logits), max(logits.stride(0), V), ptr(None if rows is None else c(rows)),
+        ptr(None if active is None else c(active)), ptr(c(prompt)), ptr(c(prompt_len)),
+        ptr(c(out)), ptr(c(n_out)), ptr(None if extra is None else c(extra)),
+        ptr(None if extra is None else c(n_extra)), ptr(c(bad)), ptr(c(bad_len)), ptr(c(ngram)),
+        B, V, R, P, cap, W, stream_ptr()), op)
+    return logits
+
+
+def stop_check(out, n_out, pos, stops, stop_len, hit, active=None, lens=None, done=None,
+               max_span=None):
+    """Cuts each row's output after its first completed stop sequence, IN PLACE: among the
+    ends e in ``(pos[r], n_out[r]]`` (at most ``max_span`` of them; None: all) the smallest at
+    which some ``stops[r, q, :stop_len[r, q]]`` ends wins, and there the lowest q. Then
+    ``n_out[r] = e``, ``hit[r] = q`` and, where given, ``active[r] = 0`` (uint8 [R]),
+    ``lens[r] = SLOT_INACTIVE`` (int32 [R]) and ``done[r] = 1`` (uint8 [R]); ``pos[r]`` becomes
+    the new ``n_out[r]`` (the last end checked, after a ``max_span`` cut). ``out`` int64 [R,
+    cap]; ``n_out``, ``pos``, ``hit`` int32 [R]; ``stops`` int32 [R, ``SEQ_MAX``,
+    ``SEQ_MAX_LEN``], ``stop_len`` int32 [R, ``SEQ_MAX``] (0: unused). ``active`` and ``done``
+    are never read. Semantics: ``reference.stop_check``, exactly. Returns ``(n_out, pos,
+    hit)``.
+
+    HIP kernel (ops/csrc/seq_rules.hip: one launch, one wave per row, every index checked on
+    the device, no host sync, capturable) for GPU tensors; CPU tensors use the reference."""
+    op = "stop_check"
+    if not isinstance(out, torch.Tensor) or out.dim() != 2 or out.shape[0] < 1 or \
+            out.shape[1] < 1 or out.dtype != torch.int64:
+        raise ValueError(f"{op}: out must be an int64 tensor [R, cap]")
+    R, cap = out.shape
+    _seq_tables(op, ("stops", "stop_len"), stops, stop_len, R, out)
+    written = [("n_out", n_out, torch.int32), ("pos", pos, torch.int32),
+               ("hit", hit, torch.int32)]
+    for name, t, dt in (("active", active, torch.uint8), ("lens", lens, torch.int32),
+                        ("done", done, torch.uint8)):
+        if t is not None:
+            written.append((name, t, dt))
+    for name, t, dt in written:
+        _int_vec(name, op, t, R, out, dt)
+        if not t.is_contiguous():
+            raise ValueError(f"{op}: {name} is written in place and must be contiguous")
+    if max_span is not None and (isinstance(max_span, bool) or not isinstance(max_span, int)
+                                 or max_span < 0):
+        raise ValueError(f"{op}: max_span must be an int >= 0 or None, got {max_span!r}")
+    if not _hip(out):
+        return ref.stop_check(out, n_out, pos, stops, stop_len, hit, active, lens, done,
+                              max_span)
+    L = _seq_library()
+    c = torch.Tensor.contiguous
+    check(L.ra_stop_check(ptr(c(out)), ptr(n_out), ptr(pos), ptr(c(stops)), ptr(c(stop_len)),
+                          ptr(hit), ptr(active), ptr(lens), ptr(done), R, cap,
+                          cap if max_span is None else min(max_span, cap), stream_ptr()), op)
+    return n_out, pos, hit
+
+
 # --------------------------------------------------------------------- cross entropy
 class _CrossEntropy(torch.autograd.Function):
     @staticmethod

@@ -671,6 +671,139 @@ def grammar_mask(logits, table, state, rows=None, extra=None, n_extra=None, acti
     return logits
 
 
+SEQ_MAX = 8      # ops/csrc/seq_rules.hip kSeqMax: sequences per row and kind
+SEQ_MAX_LEN = 8  # kSeqMaxLen there: tokens per sequence, and the longest no-repeat n-gram
+
+
+def seq_ban(logits, prompt, prompt_len, out, n_out, bad, bad_len, ngram, rows=None, extra=None,
+            n_extra=None, active=None, vocab_size=None):
+    """Banned token sequences and no-repeat n-grams (ops/csrc/seq_rules.hip semantics): the
+    single definition. Edits ``logits`` IN PLACE and returns it. No host sync.
+
+    ``logits`` [B, Vs], of which the first ``V = vocab_size or Vs`` columns count. ``rows``,
+    ``extra``, ``n_extra`` and ``active`` as in ``logit_process``: the context of logits row b,
+    with ``r = rows[b]``, is ``c = prompt[r, :prompt_len[r]] ++ out[r, :n_out[r]] ++ extra[b,
+    :n_extra[b]]``, of length C. ``bad`` int32 [R, SEQ_MAX, SEQ_MAX_LEN] with ``bad_len`` int32
+    [R, SEQ_MAX] (0, or anything outside ``1..SEQ_MAX_LEN``: unused), ``ngram`` int32 [R].
+
+    * banned sequence q of length L: if ``L - 1 <= C`` and the last ``L - 1`` context tokens
+      equal ``bad[r, q, :L-1]``, token ``bad[r, q, L-1]`` is banned (L = 1: always).
+    * no-repeat with ``n = ngram[r]`` in ``1..SEQ_MAX_LEN``: for every i in ``[0, C - n]`` with
+      ``c[i : i+n-1] == c[C-n+1 : C]``, token ``c[i+n-1]`` is banned (the Hugging Face rule,
+      over prompt and output; n = 1 bans every context token, C < n nothing).
+
+    A banned id inside ``[0, V)`` gets the dtype's ``-inf``; one outside is ignored, and every
+    other byte of the buffer keeps its bits. A row keeps all its bytes when ``active[b] ==
+    0``, ``rows[b]`` is outside ``[0, R)``, ``prompt_len`` / ``n_out`` / ``n_extra`` is
+    negative or exceeds its table, or ``ngram[r]`` is outside ``0..SEQ_MAX_LEN``."""
+    B, Vs = logits.shape
+    V = Vs if vocab_size is None else int(vocab_size)
+    dev = logits.device
+    R, P = prompt.shape
+    cap = out.shape[1]
+    Q, ML = bad.shape[1], bad.shape[2]
+    r = torch.arange(B, device=dev) if rows is None else rows.long()
+    ok = (r >= 0) & (r < R)
+    if active is not None:
+        ok = ok & active.bool()
+    rc = r.clamp(0, R - 1)
+    pl, no, n = prompt_len[rc].long(), n_out[rc].long(), ngram[rc].long()
+    ok = ok & (pl >= 0) & (pl <= P) & (no >= 0) & (no <= cap) & (n >= 0) & (n <= ML)
+    parts = [prompt[rc].long(), out[rc].long()]
+    W, ne = 0, torch.zeros_like(no)
+    if extra is not None:
+        W = extra.shape[1]
+        ne = n_extra.long()
+        ok = ok & (ne >= 0) & (ne <= W)
+        parts.append(extra.long())
+    T = P + cap + W
+    # the context, left-aligned: ctx[b, i] = c[i] for i < C; column T is spare
+    pl, no, ne = (torch.where(ok, t, torch.zeros_like(t)).unsqueeze(1) for t in (pl, no, ne))
+    C = pl + no + ne
+    i = torch.arange(T + 1, device=dev).unsqueeze(0)
+    src = torch.where(i < pl, i, torch.where(i < pl + no, P + i - pl, P + cap + i - pl - no))
+    full = torch.cat(parts + [torch.zeros(B, 1, dtype=torch.int64, device=dev)], 1)
+    ctx = full.gather(1, src.clamp(0, T))
+
+    def at(j):
+        return ctx.gather(1, j.clamp(0, T))
+
+    banned = torch.zeros(B, V + 1, dtype=torch.bool, device=dev)
+    yes = torch.ones(1, dtype=torch.bool, device=dev)
+
+    def ban(tok, when):
+        tok = torch.where(when & (tok >= 0) & (tok < V), tok, V)
+        banned.scatter_(1, tok, yes.expand_as(tok))
+
+    n = n.unsqueeze(1)
+    match = ok.unsqueeze(1) & (n >= 1) & (i <= C - n)
+    for k in range(ML - 1):
+        match = match & ((k >= n - 1) | (at(i + n - 2 - k) == at(C - 1 - k)))
+    ban(at(i + n - 1), match)
+    for q in range(Q):
+        L = bad_len[rc, q].long().unsqueeze(1)
+        use = ok.unsqueeze(1) & (L >= 1) & (L <= ML) & (L - 1 <= C)
+        seq = bad[rc, q].long()
+        for k in range(ML - 1):
+            use = use & ((k >= L - 1) | (at(C - L + 1 + k) == seq[:, k: k + 1]))
+        ban(seq.gather(1, (L - 1).clamp(0, ML - 1)), use)
+    idt = _BITS[logits.dtype][0]
+    ninf = torch.full((), float("-inf"), dtype=logits.dtype, device=dev).view(idt)
+    raw = logits[:, :V].view(idt)
+    raw.copy_(torch.where(banned[:, :V], ninf, raw))
+    return logits
+
+
+def stop_check(out, n_out, pos, stops, stop_len, hit, active=None, lens=None, done=None,
+               max_span=None):
+    """Stop sequences (ops/csrc/seq_rules.hip semantics): the single definition. Cuts each
+    row's output after the first completed stop sequence, IN PLACE. No host sync.
+
+    ``out`` int64 [R, cap]; ``n_out``, ``pos``, ``hit`` int32 [R]; ``stops`` int32 [R, SEQ_MAX,
+    SEQ_MAX_LEN] with ``stop_len`` int32 [R, SEQ_MAX] (anything outside ``1..SEQ_MAX_LEN``:
+    unused). Per row the output ends e in ``(pos, n_out]`` are looked at in ascending order
+    (at most ``max_span`` of them; None: all): e matches when some sequence q with ``1 <= L_q
+    <= e`` has ``out[e-L_q : e] == stops[q, :L_q]`` (a match may begin before ``pos``; only
+    its end is new). The smallest matching e wins, and there the lowest q: ``n_out = e``,
+    ``hit = q`` and, where given, ``active = 0`` (uint8), ``lens = SLOT_INACTIVE`` (int32),
+    ``done = 1`` (uint8). ``pos`` becomes the new ``n_out``, or the last end that was checked
+    when ``max_span`` cut the look short. ``active`` and ``done`` are never read: a row that
+    was retired at a later EOS is still cut at its stop. A row with ``n_out`` outside ``[0,
+    cap]`` or ``pos`` outside ``[0, n_out]`` has nothing written."""
+    R, cap = out.shape
+    Q, ML = stops.shape[1], stops.shape[2]
+    dev = out.device
+    n, p = n_out.long(), pos.long()
+    ok = (n >= 0) & (n <= cap) & (p >= 0) & (p <= n)
+    last = n if max_span is None else torch.minimum(n, p + int(max_span))
+    e = torch.arange(1, cap + 1, device=dev).view(1, cap, 1)  # the ends
+    L = stop_len.long().view(R, 1, Q)
+    m = ok.view(R, 1, 1) & (e > p.view(R, 1, 1)) & (e <= last.view(R, 1, 1)) & (L >= 1) & \
+        (L <= ML) & (L <= e)
+    ext = torch.cat([out, out.new_zeros(R, 1)], 1)
+    for k in range(ML):  # newest token first: out[e-1-k] against stops[q, L-1-k]
+        a = ext.gather(1, (e - 1 - k).clamp(0, cap).expand(R, cap, Q).reshape(R, -1))
+        s = stops.long().gather(2, (L - 1 - k).clamp(0, ML - 1).view(R, Q, 1)).view(R, 1, Q)
+        m = m & ((k >= L) | (a.view(R, cap, Q) == s))
+    none = (cap + 1) * Q
+    key = torch.where(m, e * Q + torch.arange(Q, device=dev).view(1, 1, Q), none)
+    key = key.view(R, -1).min(1).values
+    found = key < none
+    ee, qq = key // Q, key % Q
+    new_n = torch.where(found, ee, n)
+    new_p = torch.where(found, ee, last)
+    n_out.copy_(torch.where(found, new_n, n).to(torch.int32))
+    pos.copy_(torch.where(ok, new_p, p).to(torch.int32))
+    hit.copy_(torch.where(found, qq.to(torch.int32), hit))
+    if active is not None:
+        active.masked_fill_(found, 0)
+    if lens is not None:
+        lens.masked_fill_(found, SLOT_INACTIVE)
+    if done is not None:
+        done.masked_fill_(found, 1)
+    return n_out, pos, hit
+
+
 def _f(x):
     return x.to(torch.promote_types(x.dtype, torch.float32))
 

@@ -70,7 +70,18 @@ pool: the named grammars are registered at start-up, an inline one when its requ
 submitted, and it is dropped when the request ends, is cancelled or fails; a pool without
 room is that request's error. An unknown name, both fields at once, a field the app was not
 built for, and a grammar together with ``min_new_tokens > 0`` or a ``-inf`` ``logit_bias`` are
-each that request's error."""
+each that request's error.
+
+Sequence rules: a request may carry ``"stop": [[token, ...] | token, ...]`` (the answer ends
+right after the first of these sequences it completes, the sequence included),
+``"bad_words": [...]`` (the answer, or the prompt followed by the answer, never completes one)
+and ``"no_repeat_ngram_size": n`` (no n-gram occurs twice in prompt plus answer), with the
+limits of ``GPT2.generate``. The static server routes such a batch through the device sampler;
+``"stop"`` needs ``build_gpt2_app(..., eos_token_id=E)`` and its requests run with the grammar
+requests, apart from their batch-mates (their call ends rows at E), each row cut after its
+stop or its E. The continuous server needs ``build_gpt2_app(..., continuous=True,
+sequence_rules=True)``. A bad value, a field the app was not built for, and a grammar together
+with ``"bad_words"`` or ``"no_repeat_ngram_size" > 0`` are each that request's error."""
 
 from __future__ import annotations
 
@@ -168,6 +179,31 @@ def _request_grammar(cfg, r, grammars, eos, ctl, new, hint):
                            checked_controls(cfg.vocab_size, new, eos, **ctl) if ctl else None)
 
 
+SEQUENCE_FIELDS = ("stop", "bad_words", "no_repeat_ngram_size")
+
+
+def _request_sequences(cfg, r, eos, dfa=None, enabled=True):
+    """The request's sequence-rule fields as ``generate`` / ``submit`` keyword arguments,
+    checked, sequences as lists of lists (``{}``: it names none); ``dfa``: the request's
+    grammar, which goes with ``"stop"`` only."""
+    from ray_amd.models.gpt2 import checked_grammar_sequences, checked_sequences
+
+    kw = {k: r[k] for k in SEQUENCE_FIELDS if r.get(k) is not None}
+    if not kw:
+        return {}
+    if not enabled:
+        raise ValueError(f"{sorted(kw)[0]!r} needs build_gpt2_app(continuous=True, "
+                         "sequence_rules=True)")
+    if "stop" in kw and eos is None:
+        raise ValueError("'stop' needs build_gpt2_app(eos_token_id=...)")
+    rules = checked_sequences(cfg.vocab_size, eos, **kw)
+    checked_grammar_sequences(dfa, rules)
+    for k, v in zip(SEQUENCE_FIELDS, rules):
+        if k in kw:
+            kw[k] = v
+    return kw
+
+
 def _finite(v):
     return v if v == v and abs(v) != float("inf") else None
 
@@ -235,12 +271,14 @@ class GPT2Server:
                              "continuous=True, adapters=...)")
         return _request_params(self.model.cfg, self.seed, r)
 
-    def _run_sampled(self, reqs, params, lps=None, ctls=None, grs=None):
+    def _run_sampled(self, reqs, params, lps=None, ctls=None, grs=None, seqs=None):
         """One ragged generate call through the device sampler, every parameter per row.
         ``lps`` (each request's ``logprobs`` or None; not all None): the call reports the
         batch's widest and every result is a dict cut to its own. ``ctls``: each request's
-        ``_request_controls``. ``grs``: each request's ``TokenDFA``, none of them None: the
-        call ends rows at the server's EOS and every result is cut after its EOS."""
+        ``_request_controls``. ``grs``: each request's ``TokenDFA`` or None (a request with
+        ``"stop"`` only): the call ends rows at the server's EOS and every result is cut after
+        its EOS or its first completed stop sequence. ``seqs``: each request's
+        ``_request_sequences``."""
         lens = [p[0] for p in params]
         new = [p[1] for p in params]
         idx = torch.zeros(len(reqs), max(lens), dtype=torch.long)
@@ -254,14 +292,25 @@ class GPT2Server:
                 if any(k in c for c in ctls):
                     kw[k] = [c.get(k) for c in ctls]
         if grs:
-            kw.update(grammar=grs, eos_token_id=self.eos)
+            kw.update(eos_token_id=self.eos)
+            if any(g is not None for g in grs):
+                kw.update(grammar=grs)
+        if seqs is not None and any(seqs):
+            for k in SEQUENCE_FIELDS:  # per row: an entry is None or a list of lists
+                if any(s.get(k) for s in seqs):
+                    kw[k] = [s.get(k) or None for s in seqs]
 
         def cut(out):
-            """``new`` with a grammar row ending after its first EOS."""
+            """``new`` with every row ending after its first EOS or completed stop."""
             if not grs:
                 return new
-            rows = [out[b, : new[b]].tolist() for b in range(len(reqs))]
-            return [t.index(self.eos) + 1 if self.eos in t else len(t) for t in rows]
+            res = []
+            for b in range(len(reqs)):
+                t = out[b, : new[b]].tolist()
+                stops = (seqs[b].get("stop") or []) if seqs else []
+                res.append(next((e for e in range(1, len(t) + 1) if t[e - 1] == self.eos or any(
+                    len(s) <= e and t[e - len(s): e] == s for s in stops)), len(t)))
+            return res
 
         if lps is None or all(m is None for m in lps):
             out = self.model.generate(idx.to(self.device), max(new), **kw).cpu()
@@ -284,7 +333,7 @@ class GPT2Server:
         from ray_amd.ops.functional import LOGPROB_MAX_TOP
 
         results = [None] * len(reqs)
-        params, lps, ctls, grs = {}, {}, {}, {}
+        params, lps, ctls, grs, seqs = {}, {}, {}, {}, {}
         for i, r in enumerate(reqs):
             try:
                 lps[i] = _request_logprobs(r, LOGPROB_MAX_TOP)
@@ -292,20 +341,23 @@ class GPT2Server:
                 ctls[i] = _request_controls(self.model.cfg, r, p[1], None)
                 grs[i] = _request_grammar(self.model.cfg, r, self.grammars, self.eos, ctls[i],
                                           p[1], "build_gpt2_app(grammars=..., eos_token_id=...)")
+                seqs[i] = _request_sequences(self.model.cfg, r, self.eos, grs[i])
                 params[i] = p
             except Exception as e:  # noqa: BLE001  (one bad request must not fail its batch)
                 results[i] = {"error": f"{type(e).__name__}: {e}"}
         if any(p[2] > 0 or reqs[i].get("top_p") is not None or reqs[i].get("seed") is not None
-               or lps[i] is not None or ctls[i] or grs[i] is not None
+               or lps[i] is not None or ctls[i] or grs[i] is not None or seqs[i]
                for i, p in params.items()):
             # one call, split only where the longest prompt and the longest continuation
             # of the batch together would not fit the model's positions; the requests with a
-            # grammar run apart (their call ends rows at EOS, their batch-mates' does not)
+            # grammar or a stop run apart (their call ends rows at EOS, their batch-mates'
+            # does not)
+            ends = {i: grs[i] is not None or "stop" in seqs[i] for i in params}
             chunks = []
             for constrained in (False, True):
                 cur = []
                 for i in params:
-                    if (grs[i] is not None) != constrained:
+                    if ends[i] != constrained:
                         continue
                     trial = cur + [i]
                     if cur and max(params[j][0] for j in trial) + \
@@ -321,8 +373,9 @@ class GPT2Server:
                                             [params[i] for i in members],
                                             [lps[i] for i in members],
                                             [ctls[i] for i in members],
-                                            [grs[i] for i in members
-                                             if grs[i] is not None] or None)
+                                            [grs[i] for i in members]
+                                            if ends[members[0]] else None,
+                                            [seqs[i] for i in members])
                     for i, res in zip(members, got):
                         results[i] = res
                 except ValueError as e:
@@ -393,7 +446,8 @@ class GPT2EngineServer:
     def __init__(self, config="small", state_dict_path=None, seed=0, slots=None,
                  eos_token_id=None, device=None, poll_every=None, prefixes=None,
                  prefill_chunk=None, adapters=None, lora_rank=16, speculate=0, ngram=(2, 4),
-                 logprobs=None, logit_processors=False, grammars=None, grammar_states=0):
+                 logprobs=None, logit_processors=False, grammars=None, grammar_states=0,
+                 sequence_rules=False):
         import queue
         import threading
 
@@ -415,6 +469,7 @@ class GPT2EngineServer:
         self._logprobs = logprobs  # the engine's N (None: it keeps none)
         self._logit_processors = bool(logit_processors)
         self._grammar_states = int(grammar_states)
+        self._sequence_rules = bool(sequence_rules)
         # grammar name -> TokenDFA (None: the server answers no grammar request)
         self._grammars = dict(grammars or {}) if self._grammar_states else None
         if grammars and not self._grammar_states:
@@ -457,7 +512,8 @@ class GPT2EngineServer:
                              prefill_chunk=self._prefill_chunk, speculate=self._speculate,
                              ngram=self._ngram, logprobs=self._logprobs,
                              logit_processors=self._logit_processors,
-                             grammar_states=self._grammar_states, **kw)
+                             grammar_states=self._grammar_states,
+                             sequence_rules=self._sequence_rules, **kw)
             for name, dfa in (self._grammars or {}).items():
                 try:
                     self._gids[name] = eng.add_grammar(dfa)
@@ -570,6 +626,8 @@ class GPT2EngineServer:
             dfa = _request_grammar(self.cfg, request, self._grammars, self._eos, ctl, p[1],
                                    "build_gpt2_app(continuous=True, grammar_states=N, "
                                    "eos_token_id=...)")
+            ctl = {**ctl, **_request_sequences(self.cfg, request, self._eos, dfa,
+                                               self._sequence_rules)}
             name = request.get("prefix")
             if name is not None and (not isinstance(name, str) or name not in self._pids):
                 raise ValueError(f"unknown prefix {name!r}")
@@ -637,7 +695,8 @@ def build_gpt2_app(config="small", state_dict_path=None, seed=0, max_batch_size=
                    batch_wait_timeout_s=0.01, device=None, continuous=False, slots=None,
                    eos_token_id=None, prefixes=None, prefill_chunk=None, adapters=None,
                    lora_rank=16, speculate=0, ngram=(2, 4), logprobs=None,
-                   logit_processors=False, grammars=None, grammar_states=0):
+                   logit_processors=False, grammars=None, grammar_states=0,
+                   sequence_rules=False):
     """A Serve application around one ``GPT2Server`` replica (``serve.run`` it). ``config``
     names a ``GPT2Config`` preset; without ``state_dict_path`` the weights are the seeded
     random init. ``device`` None: the GPU assigned to the replica, else the CPU.
@@ -664,12 +723,18 @@ def build_gpt2_app(config="small", state_dict_path=None, seed=0, max_batch_size=
     ``"grammar": "name"`` or carry inline ``"choices"``, and answers with a word of it. The
     continuous server also needs ``grammar_states=N``, the rows of the engine's pool (about
     100 KB each at GPT-2's vocabulary): the named grammars' states plus room for the inline
-    grammars of the requests in flight."""
+    grammars of the requests in flight. ``sequence_rules=True`` (with ``continuous=True``): the
+    engine keeps the per-slot tables of ``"stop"``, ``"bad_words"`` and
+    ``"no_repeat_ngram_size"``, and a request may name them; the static server needs no option
+    (``"stop"`` needs ``eos_token_id`` on both)."""
     if continuous:
         dep = deployment(GPT2EngineServer, name="GPT2EngineServer")
         return dep.bind(config, state_dict_path, seed, slots, eos_token_id, device, None,
                         prefixes, prefill_chunk, adapters, lora_rank, speculate, ngram, logprobs,
-                        logit_processors, grammars, grammar_states)
+                        logit_processors, grammars, grammar_states, sequence_rules)
+    if sequence_rules:
+        raise ValueError("sequence_rules needs continuous=True (the static server needs no "
+                         "option)")
     if prefixes or prefill_chunk is not None or adapters or speculate or grammar_states:
         raise ValueError("prefixes, prefill_chunk, adapters, speculate and grammar_states need "
                          "continuous=True")
