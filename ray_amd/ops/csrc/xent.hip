@@ -34,6 +34,7 @@ __global__ __launch_bounds__(256) void xent_fwd_kernel(const bf16_t* __restrict_
 #pragma unroll
     for (int j = 1; j < 8; ++j) bm = fmaxf(bm, v[j]);
     const float mn = fmaxf(m, bm);
+    if (mn == -INFINITY) continue;  // only -inf so far: exp(-inf - -inf) would be NaN
     float acc = s * __expf(m - mn);
 #pragma unroll
     for (int j = 0; j < 8; ++j) acc += __expf(v[j] - mn);
@@ -43,6 +44,7 @@ __global__ __launch_bounds__(256) void xent_fwd_kernel(const bf16_t* __restrict_
   for (int c = V8 * 8 + threadIdx.x; c < V; c += 256) {
     const float v = bf2f(lr[c]);
     const float mn = fmaxf(m, v);
+    if (mn == -INFINITY) continue;
     s = s * __expf(m - mn) + __expf(v - mn);
     m = mn;
   }
