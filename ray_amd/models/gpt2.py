@@ -46,6 +46,10 @@ MI355X-first choices:
   bans the tokens that would complete a banned sequence or repeat an n-gram, between the
   logit processors and the grammar mask, and ``rf.stop_check`` ends a row whose output just
   completed a stop sequence (ops/csrc/seq_rules.hip), inside the captured step too.
+  Beam search (``generate(..., num_beams=W)``): W cache rows per prompt; ``rf.beam_step`` picks
+  each group's next beams and finished hypotheses from the logits buffer, ``rf.beam_kv_fork``
+  copies cached positions for the beams that changed rows (ops/csrc/beam.hip), both inside the
+  captured step, and ``rf.beam_backtrace`` reads the result out at the end.
   The three inference passes (prompt, extend, decode) run ONE layer loop, ``_layers``, and
   hand it their attention step; the training ``forward`` keeps its own (autograd ops).
 """
@@ -275,6 +279,45 @@ class _SeededSampler:
 
     def capture(self):
         self.graph = CapturedStep(self._step, self.out.device)
+
+    def __call__(self):
+        if self.graph is None:
+            self._step()
+        else:
+            self.graph.replay()
+
+
+class _BeamSearch:
+    """The step of ``generate(num_beams=W)`` over a cache of B * W rows (row ``g * W + w``):
+    ``decode_step`` of the tokens the last step chose, back into the static logits buffer,
+    ``rf.beam_step`` over it (candidates, finished hypotheses, live beams and their slots)
+    and ``rf.beam_kv_fork`` (a beam that moved to another slot gets its parent's cached
+    positions; a beam that kept its slot moves nothing). Nothing in it touches the host, so
+    ``capture`` records it in ONE HIP graph and a token costs one replay."""
+
+    def __init__(self, model, cache, logits, B, W, max_new_tokens, eos, length_penalty,
+                 early_stopping, adapters=None):
+        cfg = model.cfg
+        dev = logits.device
+        self.model, self.cache, self.adapters = model, cache, adapters
+        self.buf = torch.empty(B * W, cfg.padded_vocab, device=dev, dtype=logits.dtype)
+        self.logits = self.buf[:, : cfg.vocab_size]
+        self.logits.copy_(logits)
+        self.state = rf.beam_state(B, W, max_new_tokens, eos, length_penalty, early_stopping, dev)
+        self.graph = None
+        self._choose()  # the first token, from the prompt's logits
+
+    def _choose(self):
+        rf.beam_step(self.logits, self.state)
+        rf.beam_kv_fork(self.cache.k, self.cache.v, self.state["parent"], self.cache.lens)
+
+    def _step(self):
+        self.model.decode_step(self.state["tok"], self.cache, out=self.buf,
+                               adapters=self.adapters)
+        self._choose()
+
+    def capture(self):
+        self.graph = CapturedStep(self._step, self.buf.device)
 
     def __call__(self):
         if self.graph is None:
@@ -541,6 +584,28 @@ class SequenceRules:
     def check(self, out, n_out, **kw):
         """``rf.stop_check`` on ``out`` / ``n_out`` with these tables."""
         return rf.stop_check(out, n_out, self.pos, self.stops, self.stop_len, self.hit, **kw)
+
+
+def checked_beams(vocab_size, eos_token_id, num_beams, length_penalty=1.0, early_stopping=True,
+                  num_return_sequences=1):
+    """The beam-search arguments of a request, validated: ``(num_beams, length_penalty,
+    early_stopping, num_return_sequences)``; raises ``ValueError`` otherwise."""
+    def is_int(v):
+        return isinstance(v, int) and not isinstance(v, bool)
+
+    if not is_int(num_beams) or not 1 <= num_beams <= rf.BEAM_MAX:
+        raise ValueError(f"num_beams must be an int in 1..{rf.BEAM_MAX}, got {num_beams!r}")
+    if not is_int(eos_token_id) or not 0 <= eos_token_id < vocab_size:
+        raise ValueError("num_beams needs eos_token_id, a token of the vocabulary")
+    if isinstance(length_penalty, bool) or not isinstance(length_penalty, (int, float)) or \
+            not math.isfinite(length_penalty):
+        raise ValueError(f"length_penalty must be a finite number, got {length_penalty!r}")
+    if not isinstance(early_stopping, bool):
+        raise ValueError(f"early_stopping must be a bool, got {early_stopping!r}")
+    if not is_int(num_return_sequences) or not 1 <= num_return_sequences <= num_beams:
+        raise ValueError(f"num_return_sequences must be an int in 1..num_beams, got "
+                         f"{num_return_sequences!r}")
+    return num_beams, float(length_penalty), early_stopping, num_return_sequences
 
 
 def _per_row_sequences(name, value, B):
@@ -900,7 +965,8 @@ class GPT2(nn.Module):
                  top_p=None, seeds=None, eos_token_id=None, generator=None, graph=False,
                  adapters=None, logprobs=None, repetition_penalty=None, presence_penalty=None,
                  frequency_penalty=None, min_new_tokens=None, logit_bias=None, grammar=None,
-                 stop=None, bad_words=None, no_repeat_ngram_size=None):
+                 stop=None, bad_words=None, no_repeat_ngram_size=None, num_beams=None,
+                 length_penalty=1.0, early_stopping=True, num_return_sequences=1):
         """Autoregressive generation with a KV cache: ``idx`` [B, T] prompts, right-padded
         to a common length with true lengths ``lens`` (default: all T). Returns the new
         tokens [B, max_new_tokens] (int64). ``temperature`` 0 is greedy, otherwise samples
@@ -969,12 +1035,43 @@ class GPT2(nn.Module):
         (ops/csrc/seq_rules.hip), both on the device and inside the captured step: a row's
         tokens depend on that row alone and a token still costs one replay. ``logprobs=``
         reports the banned distribution. A grammar goes with ``stop`` only. With none of
-        the three given not one extra op runs."""
+        the three given not one extra op runs.
+
+        Beam search: ``num_beams=W`` (1..``rf.BEAM_MAX``; needs ``eos_token_id``) returns
+        ``(tokens int64 [B, R, max_new_tokens], scores fp32 [B, R], lengths int32 [B, R])``, the
+        ``R = num_return_sequences`` (1..W) best hypotheses per prompt, best first, right-padded
+        with EOS; a hypothesis that ended with EOS counts it in its length. A hypothesis's score
+        is the sum of its tokens' log-probabilities divided by ``length ** length_penalty``.
+        With ``early_stopping=True`` a prompt is finished once it holds W finished hypotheses,
+        with ``False`` only when none of its live beams can still beat the worst of them at
+        the current length. The prompt is prefilled once and ``rf.kv_copy`` replicates its
+        cache rows to the W beams; a step is ``decode_step``, ``rf.beam_step`` and
+        ``rf.beam_kv_fork`` (ops/csrc/beam.hip), with ``graph=True`` one replay per token and
+        no host read before the result. ``adapters`` is per prompt. Beams permute their
+        token histories every step, which the per-row history tables of the other controls do
+        not follow: ``num_beams`` with ``seeds``, ``generator``, a non-zero ``temperature``,
+        ``top_k``, ``top_p``, ``logprobs``, a logit processor, ``grammar`` or a sequence rule
+        is a ``ValueError``. With ``num_beams=None`` not one extra op runs."""
         cfg = self.cfg
         B, T = idx.shape
         if logprobs is not None:
             _checked_top_n("logprobs", logprobs)
         ad = self._adapter_tensor(adapters, B, idx.device)
+        if num_beams is not None:
+            given = {"seeds": seeds, "generator": generator, "top_k": top_k, "top_p": top_p,
+                     "logprobs": logprobs, "repetition_penalty": repetition_penalty,
+                     "presence_penalty": presence_penalty,
+                     "frequency_penalty": frequency_penalty, "min_new_tokens": min_new_tokens,
+                     "logit_bias": logit_bias, "grammar": grammar, "stop": stop,
+                     "bad_words": bad_words, "no_repeat_ngram_size": no_repeat_ngram_size}
+            for k, v in given.items():
+                if v is not None:
+                    raise ValueError(f"num_beams does not go with {k}")
+            if isinstance(temperature, (list, tuple, torch.Tensor)) or temperature != 0:
+                raise ValueError("num_beams does not go with a temperature: beam search is "
+                                 "deterministic")
+            checked_beams(cfg.vocab_size, eos_token_id, num_beams, length_penalty,
+                          early_stopping, num_return_sequences)
         named = {k: v for k, v in (("repetition_penalty", repetition_penalty),
                                    ("presence_penalty", presence_penalty),
                                    ("frequency_penalty", frequency_penalty),
@@ -1022,6 +1119,25 @@ class GPT2(nn.Module):
         if graph and not idx.is_cuda:
             raise ValueError("graph=True needs the model and prompts on the GPU")
         dev = idx.device
+        if num_beams is not None:
+            W = num_beams
+            lens_t = torch.tensor(lens_l, dtype=torch.int32, device=dev)
+            first = KVCache(cfg, B, max(lens_l), dev, self.wte.dtype)
+            logits = self.prefill(idx, lens_t, first, adapters=ad)
+            cache = KVCache(cfg, B * W, max(lens_l) + max_new_tokens, dev, self.wte.dtype)
+            cache.lens = lens_t.repeat_interleave(W)
+            rf.kv_copy(first.k, first.v, cache.k, cache.v,
+                       torch.arange(B, dtype=torch.int32, device=dev).repeat_interleave(W),
+                       cache.rows, cache.lens)
+            step = _BeamSearch(self, cache, logits.repeat_interleave(W, 0), B, W,
+                               max_new_tokens, int(eos_token_id), float(length_penalty),
+                               bool(early_stopping),
+                               None if ad is None else ad.repeat_interleave(W))
+            for t in range(1, max_new_tokens):
+                if graph and t == 2:  # (step 1 ran eagerly and warmed up what the capture needs)
+                    step.capture()
+                step()
+            return rf.beam_backtrace(step.state, num_return_sequences)
         ctl = rows_c = None
         if named:
             cols = {k: _per_row(k, v, None, B, lambda x: x) if k != "logit_bias" or

@@ -148,6 +148,10 @@ _SIGS = {
     "ra_seq_max_len": [],
     "ra_seq_ban": [c_void_p, c_long] + [c_void_p] * 11 + [c_int] * 6 + [c_void_p],
     "ra_stop_check": [c_void_p] * 9 + [c_int] * 3 + [c_void_p],
+    "ra_beam_max": [],
+    "ra_beam_step": [c_void_p, c_long, c_int] + [c_void_p] * 15 + [c_int] * 5 + [c_void_p],
+    "ra_beam_kv_fork": [c_void_p] * 4 + [c_int] * 4 + [c_void_p],
+    "ra_beam_backtrace": [c_void_p] * 14 + [c_int] * 5 + [c_void_p],
     "ra_gemm_nt": [c_void_p, c_long, c_void_p, c_long, c_void_p, c_long, c_int, c_int, c_int,
                    c_int, c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_int, c_int,
                    c_void_p],

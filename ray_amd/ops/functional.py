@@ -1535,6 +1535,161 @@ def stop_check(out, n_out, pos, stops, stop_len, hit, active=None, lens=None, do
     return n_out, pos, hit
 
 
+BEAM_MAX = ref.BEAM_MAX  # ops/csrc/beam.hip kMaxW (checked against the library)
+
+_BEAM_SHAPES = (("len_norm", torch.float32, "M1"), ("score", torch.float32, "N"),
+                ("tok", torch.int64, "N"), ("parent", torch.int32, "N"),
+                ("tok_hist", torch.int32, "MN"), ("par_hist", torch.int32, "MN"),
+                ("hyp_score", torch.float32, "GW"), ("hyp_step", torch.int32, "GW"),
+                ("hyp_par", torch.int32, "GW"), ("hyp_ord", torch.int32, "GW"),
+                ("hyp_n", torch.int32, "G"), ("done", torch.uint8, "G"),
+                ("step", torch.int32, "G"), ("cand_tok", torch.int32, "NK"),
+                ("cand", torch.float32, "NK"))
+
+
+def beam_state(groups, num_beams, max_new_tokens, eos_token_id, length_penalty=1.0,
+               early_stopping=True, device=None):
+    """The state dict of a beam search over ``groups`` prompts of ``num_beams``
+    (1..``BEAM_MAX``) beams, for ``beam_step`` / ``beam_backtrace``: see
+    ``reference.beam_state`` for its entries."""
+    for name, v, lo in (("groups", groups, 1), ("num_beams", num_beams, 1),
+                        ("max_new_tokens", max_new_tokens, 1), ("eos_token_id", eos_token_id, 0)):
+        if isinstance(v, bool) or not isinstance(v, int) or v < lo:
+            raise ValueError(f"beam_state: {name} must be an int >= {lo}, got {v!r}")
+    if num_beams > BEAM_MAX:
+        raise ValueError(f"beam_state: num_beams must be in 1..{BEAM_MAX}, got {num_beams}")
+    lp = float(length_penalty)
+    if lp != lp or lp in (float("inf"), float("-inf")):
+        raise ValueError("beam_state: length_penalty must be finite")
+    return ref.beam_state(groups, num_beams, max_new_tokens, eos_token_id, lp,
+                          bool(early_stopping), device)
+
+
+def _beam_checked(op, st, like):
+    """``st`` as a ``beam_state`` on ``like``'s device: returns (G, W, max_new)."""
+    if not isinstance(st, dict) or not all(k in st for k in ("W", "eos", "early", "max_new")):
+        raise ValueError(f"{op}: state must be a beam_state dict")
+    W, M = st["W"], st["max_new"]
+    if not 1 <= W <= BEAM_MAX or M < 1 or st["eos"] < 0:
+        raise ValueError(f"{op}: the state's W, max_new or eos is out of range")
+    done = st.get("done")
+    if not isinstance(done, torch.Tensor) or done.dim() != 1 or done.shape[0] < 1:
+        raise ValueError(f"{op}: state['done'] must be a uint8 tensor [G]")
+    G = done.shape[0]
+    N = G * W
+    shapes = {"M1": (M + 1,), "N": (N,), "MN": (M, N), "GW": (G, W), "G": (G,), "NK": (N, 2 * W)}
+    for name, dt, sh in _BEAM_SHAPES:
+        t = st.get(name)
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) != shapes[sh] or t.dtype != dt or \
+                t.device != like.device or not t.is_contiguous():
+            raise ValueError(f"{op}: state[{name!r}] must be a contiguous {dt} tensor "
+                             f"{list(shapes[sh])} on {like.device}")
+    return G, W, M
+
+
+def _beam_library():
+    L = _lib.lib()
+    assert L.ra_beam_max() == BEAM_MAX
+    return L
+
+
+def beam_step(logits, state, vocab_size=None):
+    """One beam-search step over ``logits`` [G * W, Vs] (the first ``vocab_size or Vs``
+    columns count), ``state`` a ``beam_state`` updated IN PLACE: per row the 2W best
+    continuations with their cumulative scores, per group the finished hypotheses, the W
+    live beams in slot-stable placement (``state['tok']`` is the next ``decode_step`` input,
+    ``state['parent']`` the row each row continues: ``beam_kv_fork``), the step's history
+    slice and ``done``. Semantics: ``reference.beam_step``.
+
+    Two HIP launches (ops/csrc/beam.hip: an exact top-2W radix select per row, a one-wave
+    merge per group; every index read on the device, no host sync, capturable, one capture
+    serves every step) for GPU tensors with bf16 logits of unit column stride and at most
+    ``SAMPLE_MAX_VOCAB`` columns; the rows may be a column slice of a wider buffer, read in
+    place. CPU tensors, other dtypes and wider vocabularies use the reference."""
+    op = "beam_step"
+    if not isinstance(logits, torch.Tensor) or logits.dim() != 2 or \
+            not logits.dtype.is_floating_point:
+        raise ValueError(f"{op}: logits must be a floating-point tensor [G * W, V]")
+    G, W, M = _beam_checked(op, state, logits)
+    N, Vs = logits.shape
+    V = Vs if vocab_size is None else int(vocab_size)
+    if N != G * W or V < 1 or V > Vs:
+        raise ValueError(f"{op}: logits {tuple(logits.shape)} do not fit {G} groups of {W} "
+                         f"beams and vocab_size {V}")
+    if not (_hip(logits) and logits.dtype == torch.bfloat16 and V <= SAMPLE_MAX_VOCAB):
+        return ref.beam_step(logits, state, V)
+    L = _beam_library()
+    if logits.stride(1) != 1 or (N > 1 and logits.stride(0) < V):
+        logits = logits.contiguous()
+    s = state
+    check(L.ra_beam_step(ptr(logits), max(logits.stride(0), V), V, ptr(s["cand_tok"]),
+                         ptr(s["cand"]), ptr(s["len_norm"]), ptr(s["tok"]), ptr(s["parent"]),
+                         ptr(s["score"]), ptr(s["tok_hist"]), ptr(s["par_hist"]),
+                         ptr(s["hyp_score"]), ptr(s["hyp_step"]), ptr(s["hyp_par"]),
+                         ptr(s["hyp_ord"]), ptr(s["hyp_n"]), ptr(s["done"]), ptr(s["step"]),
+                         G, W, M, s["eos"], int(s["early"]), stream_ptr()), op)
+
+
+def beam_kv_fork(k, v, parent, lens):
+    """Re-parents cache rows after a ``beam_step``, IN PLACE: ``k``, ``v`` [L, S, H, Tmax, D],
+    ``parent`` and ``lens`` int32 [S] on their device. Every row r whose ``parent[r] = p`` is
+    another row of the cache that keeps itself (``parent[p] == p``), with 0 < lens[r] <= Tmax,
+    gets positions ``[0, lens[r])`` of row p, all layers, K and V, bitwise; a row whose parent is
+    itself, out of range or itself a destination writes nothing, and nothing else is written.
+    Bytes move only for the beams that fork. Semantics: ``reference.beam_kv_fork``.
+
+    One HIP launch (ops/csrc/beam.hip; the vectors are read on the device: capturable) for
+    bf16, D == 64 GPU tensors; CPU tensors, other dtypes and head sizes use the reference."""
+    op = "beam_kv_fork"
+    for name, t in (("k", k), ("v", v)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 5:
+            raise ValueError(f"{op}: {name} must be [L, S, H, Tmax, D]")
+    if k.shape != v.shape or k.dtype != v.dtype or k.device != v.device or min(k.shape) < 1:
+        raise ValueError(f"{op}: k and v must be non-empty and share a shape, a dtype and a device")
+    Ln, S, H, Tmax, D = k.shape
+    _int_vec("parent", op, parent, S, k)
+    _int_vec("lens", op, lens, S, k)
+    if not (_hip(k) and k.dtype == torch.bfloat16 and D == 64):
+        return ref.beam_kv_fork(k, v, parent, lens)
+    if not (k.is_contiguous() and v.is_contiguous()):
+        raise ValueError(f"{op}: the caches are written in place and must be contiguous")
+    if Ln * H > 65535 or S > 65535:
+        raise ValueError(f"{op}: L * H and S must not exceed 65535")
+    check(_beam_library().ra_beam_kv_fork(ptr(k), ptr(v), ptr(parent.contiguous()),
+                                          ptr(lens.contiguous()), Ln, H, S, Tmax, stream_ptr()),
+          op)
+
+
+def beam_backtrace(state, num_return_sequences=1):
+    """The result of a beam search: finalises ``state`` (which is only read; a group that is
+    not done offers its live beams) and returns the ``R = num_return_sequences`` (1..W) best
+    hypotheses per group as ``(tokens int64 [G, R, max_new]`` right-padded with EOS, ``scores
+    fp32 [G, R], lengths int32 [G, R])``. Semantics: ``reference.beam_backtrace``.
+
+    One HIP launch (ops/csrc/beam.hip, one thread per returned hypothesis) for a state on
+    the GPU; the reference otherwise."""
+    op = "beam_backtrace"
+    like = state.get("score") if isinstance(state, dict) else None
+    if not isinstance(like, torch.Tensor):
+        raise ValueError(f"{op}: state must be a beam_state dict")
+    G, W, M = _beam_checked(op, state, like)
+    R = num_return_sequences
+    if isinstance(R, bool) or not isinstance(R, int) or not 1 <= R <= W:
+        raise ValueError(f"{op}: num_return_sequences must be an int in 1..{W}, got {R!r}")
+    if not _hip(like):
+        return ref.beam_backtrace(state, R)
+    s, dev = state, like.device
+    out = torch.empty(G, R, M, dtype=torch.int64, device=dev)
+    out_s = torch.empty(G, R, dtype=torch.float32, device=dev)
+    out_n = torch.empty(G, R, dtype=torch.int32, device=dev)
+    check(_beam_library().ra_beam_backtrace(
+        ptr(s["len_norm"]), ptr(s["score"]), ptr(s["tok_hist"]), ptr(s["par_hist"]),
+        ptr(s["hyp_score"]), ptr(s["hyp_step"]), ptr(s["hyp_par"]), ptr(s["hyp_ord"]),
+        ptr(s["hyp_n"]), ptr(s["done"]), ptr(s["step"]), ptr(out), ptr(out_s), ptr(out_n),
+        G, W, M, s["eos"], R, stream_ptr()), op)
+    return out, out_s, out_n
+
+
 # --------------------------------------------------------------------- cross entropy
 class _CrossEntropy(torch.autograd.Function):
     @staticmethod

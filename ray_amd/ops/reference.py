@@ -804,6 +804,224 @@ def stop_check(out, n_out, pos, stops, stop_len, hit, active=None, lens=None, do
     return n_out, pos, hit
 
 
+BEAM_MAX = 8  # ops/csrc/beam.hip kMaxW: beams per group
+
+_BEAM_TABLES = ("hyp_score", "hyp_step", "hyp_par", "hyp_ord")
+
+
+def beam_state(groups, num_beams, max_new_tokens, eos_token_id, length_penalty=1.0,
+               early_stopping=True, device=None):
+    """The state of a beam search over ``groups`` prompts of ``num_beams`` = W beams, row
+    ``r = g * W + w``: a dict of the scalars ``W``, ``eos``, ``early``, ``max_new`` and of the
+    tensors that ``beam_step`` updates IN PLACE:
+
+    * ``score`` fp32 [N] (starts at 0 for beam 0 of a group, -inf for the others), ``tok`` int64
+      [N] (the next ``decode_step`` input), ``parent`` int32 [N] (the row each row continues);
+    * ``tok_hist``, ``par_hist`` int32 [max_new, N], one slice per step;
+    * the finished hypotheses ``hyp_score`` fp32, ``hyp_step``, ``hyp_par``, ``hyp_ord`` int32
+      [G, W] with ``hyp_n`` int32 [G], the number accepted so far (min(hyp_n, W) are held);
+    * ``done`` uint8 [G], ``step`` int32 [G], the steps a group has taken;
+    * ``len_norm`` fp32 [max_new + 1], ``L ** length_penalty`` evaluated in fp64 and rounded
+      once; ``cand_tok`` int32 and ``cand`` fp32 [N, 2W], each row's candidates of the last step.
+    """
+    G, W, M = int(groups), int(num_beams), int(max_new_tokens)
+    N = G * W
+    i32 = dict(dtype=torch.int32, device=device)
+    norm = torch.arange(M + 1, dtype=torch.float64).pow(float(length_penalty))
+    norm[0] = 1.0  # never read: a hypothesis holds a token at least
+    score = torch.full((G, W), float("-inf"), dtype=torch.float32, device=device)
+    score[:, 0] = 0.0
+    return {
+        "W": W, "eos": int(eos_token_id), "early": bool(early_stopping), "max_new": M,
+        "len_norm": norm.to(torch.float32).to(device), "score": score.view(N),
+        "tok": torch.zeros(N, dtype=torch.int64, device=device),
+        "parent": torch.arange(N, **i32),
+        "tok_hist": torch.zeros(M, N, **i32), "par_hist": torch.zeros(M, N, **i32),
+        "hyp_score": torch.full((G, W), float("-inf"), dtype=torch.float32, device=device),
+        "hyp_step": torch.zeros(G, W, **i32), "hyp_par": torch.zeros(G, W, **i32),
+        "hyp_ord": torch.zeros(G, W, **i32), "hyp_n": torch.zeros(G, **i32),
+        "done": torch.zeros(G, dtype=torch.uint8, device=device), "step": torch.zeros(G, **i32),
+        "cand_tok": torch.full((N, 2 * W), -1, **i32),
+        "cand": torch.full((N, 2 * W), float("-inf"), dtype=torch.float32, device=device),
+    }
+
+
+def _f32_div(a, b):
+    import numpy as np
+
+    with np.errstate(all="ignore"):
+        return float(np.float32(a) / np.float32(b))
+
+
+def _hyp_offer(hyp, n, W, score, step, par):
+    """The W-entry table ``hyp`` (lists of [score, step, par, ord]) with n accepted so far: a
+    new hypothesis takes a free entry, or replaces the worst (lowest score, the latest among
+    equals) if it is strictly better. Returns the new n."""
+    if n < W:
+        hyp[n] = [score, step, par, n]
+        return n + 1
+    at = 0
+    for i in range(1, W):
+        if hyp[i][0] < hyp[at][0] or (hyp[i][0] == hyp[at][0] and hyp[i][3] > hyp[at][3]):
+            at = i
+    if not score > hyp[at][0]:
+        return n
+    hyp[at] = [score, step, par, n]
+    return n + 1
+
+
+def _hyp_lists(st, keys=_BEAM_TABLES):
+    cols = [st[k].tolist() for k in keys]
+    return [[list(e) for e in zip(*rows)] for rows in zip(*cols)]
+
+
+def beam_step(logits, st, vocab_size=None):
+    """One beam-search step (ops/csrc/beam.hip semantics): the single definition, the
+    bookkeeping as plain loops. ``logits`` [N, Vs] (the first ``V = vocab_size or Vs`` columns
+    count; finite or -inf), ``st`` a ``beam_state``, updated IN PLACE.
+
+    Per row: the 2W largest logits ordered by stored value descending, then index ascending
+    (the ``token_logprobs`` order), ``lp = x - lse`` as there, rounded to fp32 once, and
+    ``cand = score[r] + lp``, one fp32 add; ``(-1, -inf)`` pads a row with V < 2W.
+
+    Per group at step t = ``step[g]``: the W * 2W candidates are ordered by cand descending,
+    beam slot ascending, in-row rank ascending, and the first 2W are walked. A padding
+    candidate is passed over. An EOS candidate of rank >= W is skipped; one of rank < W
+    becomes a hypothesis ``(cand / len_norm[t + 1], step t, parent row)`` (fp32 division),
+    accepted while the group holds fewer than W, or in place of the worst one if strictly
+    better. The first W other candidates become the live beams: in rank order each takes its
+    parent's slot if that is still free, then the rest take the lowest free slots in rank
+    order, so ``parent[r] == r`` for every surviving parent and a fork's source row is never
+    a destination. A slot left over (fewer than W candidates) holds a dead beam: EOS, score
+    -inf, its own parent. The group is done when it holds W hypotheses and, unless
+    ``early``, its worst one is >= best live cand / len_norm[t + 1]. A group that was done
+    on entry (or has taken ``max_new`` steps) emits EOS with ``parent[r] = r`` and changes
+    nothing else."""
+    W, eos, M = st["W"], st["eos"], st["max_new"]
+    K = 2 * W
+    N, Vs = logits.shape
+    G = N // W
+    V = Vs if vocab_size is None else int(vocab_size)
+    ct = torch.float64 if logits.dtype == torch.float64 else torch.float32
+    x = logits[:, :V].to(ct)
+    m = x.max(-1, keepdim=True).values
+    lse = m + torch.log(torch.exp(x - m).sum(-1, keepdim=True))
+    k = min(K, V)
+    xs, order = torch.sort(x, dim=-1, descending=True, stable=True)
+    st["cand_tok"].fill_(-1)
+    st["cand"].fill_(float("-inf"))
+    st["cand_tok"][:, :k] = order[:, :k].to(torch.int32)
+    st["cand"][:, :k] = st["score"].view(N, 1) + (xs[:, :k] - lse).to(torch.float32)
+
+    c_tok, c_val = st["cand_tok"].tolist(), st["cand"].tolist()
+    norm, steps, done = st["len_norm"].tolist(), st["step"].tolist(), st["done"].tolist()
+    hyp_n, hyps = st["hyp_n"].tolist(), _hyp_lists(st)
+    tok, parent, score = st["tok"].tolist(), st["parent"].tolist(), st["score"].tolist()
+    for g in range(G):
+        base, t = g * W, steps[g]
+        if done[g] or not 0 <= t < M:
+            for r in range(base, base + W):
+                tok[r], parent[r] = eos, r
+            continue
+        cands = [(c_val[base + w][j], w, c_tok[base + w][j]) for w in range(W) for j in range(K)]
+        cands.sort(key=lambda c: -c[0])  # stable: (w, rank) ascending among equals
+        live = []
+        for q, (val, w, tk) in enumerate(cands[:K]):
+            if tk < 0:
+                continue
+            if tk == eos:
+                if q < W:
+                    hyp_n[g] = _hyp_offer(hyps[g], hyp_n[g], W, _f32_div(val, norm[t + 1]), t,
+                                          base + w)
+            elif len(live) < W:
+                live.append((val, w, tk))
+        slot = [None] * len(live)
+        used = set()
+        for i, (_, w, _) in enumerate(live):
+            if w not in used:
+                slot[i] = w
+                used.add(w)
+        for i in range(len(live)):
+            if slot[i] is None:
+                slot[i] = min(set(range(W)) - used)
+                used.add(slot[i])
+        place = {w: (eos, base + w, float("-inf")) for w in range(W)}
+        for i, (val, w, tk) in enumerate(live):
+            place[slot[i]] = (tk, base + w, val)
+        for w, (tk, par, val) in place.items():
+            r = base + w
+            tok[r], parent[r], score[r] = tk, par, val
+            st["tok_hist"][t, r] = tk
+            st["par_hist"][t, r] = par
+        if hyp_n[g] >= W:
+            best = _f32_div(live[0][0], norm[t + 1]) if live else float("-inf")
+            if st["early"] or min(h[0] for h in hyps[g]) >= best:
+                done[g] = 1
+        steps[g] = t + 1
+    for key, val in (("tok", tok), ("parent", parent), ("score", score), ("hyp_n", hyp_n),
+                     ("done", done), ("step", steps)):
+        st[key].copy_(torch.tensor(val, dtype=st[key].dtype))
+    for i, key in enumerate(_BEAM_TABLES):
+        st[key].copy_(torch.tensor([[h[i] for h in hg] for hg in hyps], dtype=st[key].dtype))
+
+
+def beam_kv_fork(k, v, parent, lens):
+    """The cache side of a beam step (ops/csrc/beam.hip semantics): ``k``, ``v`` [L, S, H,
+    Tmax, D] written IN PLACE, ``parent``, ``lens`` integer [S]. Every row r with
+    ``parent[r] = p != r``, 0 <= p < S, ``parent[p] == p`` and 0 < lens[r] <= Tmax gets
+    ``k[l, r, h, t] = k[l, p, h, t]`` for t < lens[r] (the same for ``v``), bitwise; any other
+    row, and every other element, keeps its bits. No host sync."""
+    S, Tmax = k.shape[1], k.shape[3]
+    r = torch.arange(S, device=k.device)
+    p, ln = parent.long(), lens.long()
+    pc = p.clamp(0, S - 1)
+    ok = (p != r) & (p >= 0) & (p < S) & (p[pc] == pc) & (ln > 0) & (ln <= Tmax)
+    src = torch.where(ok, pc, r)
+    take = (ok.view(S, 1) & (torch.arange(Tmax, device=k.device).view(1, Tmax) < ln.view(S, 1)))
+    take = take.view(1, S, 1, Tmax, 1)
+    for c in (k, v):
+        c.copy_(torch.where(take, c[:, src], c))
+
+
+def beam_backtrace(st, num_return_sequences=1):
+    """Finalisation and read-out of a beam search (ops/csrc/beam.hip semantics), ``st`` is
+    only read. A group that is not done offers its W live beams, in slot order, as hypotheses
+    ``(score[r] / len_norm[n], step n, row r)`` with n = ``step[g]`` the steps it has taken,
+    under ``beam_step``'s table rule. The hypotheses are ordered by score descending, then by
+    acceptance order, and the first ``R = num_return_sequences`` are read out by following
+    ``par_hist`` / ``tok_hist`` backwards from ``(step - 1, parent row)``; one that ended with
+    EOS holds it and counts it. Returns ``(tokens int64 [G, R, max_new]`` right-padded with
+    EOS, ``scores fp32 [G, R], lengths int32 [G, R])``; ``(-inf, 0)`` where a group holds
+    fewer than R."""
+    W, eos, M, R = st["W"], st["eos"], st["max_new"], int(num_return_sequences)
+    G = st["done"].shape[0]
+    norm, steps, done = st["len_norm"].tolist(), st["step"].tolist(), st["done"].tolist()
+    hyp_n, hyps, score = st["hyp_n"].tolist(), _hyp_lists(st), st["score"].tolist()
+    tok_hist, par_hist = st["tok_hist"].tolist(), st["par_hist"].tolist()
+    out = [[[eos] * M for _ in range(R)] for _ in range(G)]
+    out_s = [[float("-inf")] * R for _ in range(G)]
+    out_n = [[0] * R for _ in range(G)]
+    for g in range(G):
+        base, n, length = g * W, hyp_n[g], max(0, min(steps[g], M))
+        if not done[g] and length > 0:
+            for w in range(W):
+                n = _hyp_offer(hyps[g], n, W, _f32_div(score[base + w], norm[length]), length,
+                               base + w)
+        held = sorted(hyps[g][: min(n, W)], key=lambda h: (-h[0], h[3]))
+        for j, (sc, s, p, _) in enumerate(held[:R]):
+            s = max(0, min(s, length))
+            out_s[g][j], out_n[g][j] = sc, (s + 1 if s < length else length)
+            for i in range(s - 1, -1, -1):
+                if not base <= p < base + W:
+                    p = base
+                out[g][j][i] = tok_hist[i][p]
+                p = par_hist[i][p]
+    dev = st["score"].device
+    return (torch.tensor(out, dtype=torch.int64, device=dev).view(G, R, M),
+            torch.tensor(out_s, dtype=torch.float32, device=dev).view(G, R),
+            torch.tensor(out_n, dtype=torch.int32, device=dev).view(G, R))
+
+
 def _f(x):
     return x.to(torch.promote_types(x.dtype, torch.float32))
 

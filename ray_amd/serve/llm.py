@@ -81,7 +81,16 @@ limits of ``GPT2.generate``. The static server routes such a batch through the d
 requests, apart from their batch-mates (their call ends rows at E), each row cut after its
 stop or its E. The continuous server needs ``build_gpt2_app(..., continuous=True,
 sequence_rules=True)``. A bad value, a field the app was not built for, and a grammar together
-with ``"bad_words"`` or ``"no_repeat_ngram_size" > 0`` are each that request's error."""
+with ``"bad_words"`` or ``"no_repeat_ngram_size" > 0`` are each that request's error.
+
+Beam search (static server, ``build_gpt2_app(..., eos_token_id=E)``): a request may carry
+``"num_beams": W`` (1..8) with ``"length_penalty"``, ``"early_stopping"`` and
+``"num_return_sequences": R`` (``GPT2.generate``'s arguments). The beam requests of a batch
+that share these and ``max_new_tokens`` run as one ``generate(num_beams=W)`` call, apart from
+their batch-mates; the response carries ``"sequences"``, the R best hypotheses, best first, each
+ending with E where it finished, their ``"scores"``, and the best one as ``"tokens"``. A bad
+value, a sampling, logit-processor, grammar or sequence-rule field next to ``"num_beams"``, and
+a beam field sent to the continuous server are each that request's error."""
 
 from __future__ import annotations
 
@@ -202,6 +211,33 @@ def _request_sequences(cfg, r, eos, dfa=None, enabled=True):
         if k in kw:
             kw[k] = v
     return kw
+
+
+BEAM_FIELDS = ("num_beams", "length_penalty", "early_stopping", "num_return_sequences")
+
+
+def _request_beams(cfg, r, eos, enabled=True):
+    """The request's checked beam-search fields as ``(num_beams, length_penalty,
+    early_stopping, num_return_sequences)`` (None: it names none). Beam search is
+    deterministic and runs without the sampler, the logit processors, grammars and sequence
+    rules: a request that names any of their fields with it is in error."""
+    from ray_amd.models.gpt2 import checked_beams
+
+    kw = {k: r[k] for k in BEAM_FIELDS if r.get(k) is not None}
+    if not kw:
+        return None
+    if not enabled:
+        raise ValueError(f"{sorted(kw)[0]!r} needs the static server: build_gpt2_app("
+                         "continuous=False, eos_token_id=...)")
+    if "num_beams" not in kw:
+        raise ValueError(f"{sorted(kw)[0]!r} needs 'num_beams'")
+    if eos is None:
+        raise ValueError("'num_beams' needs build_gpt2_app(eos_token_id=...)")
+    for k in ("temperature", "top_k", "top_p", "seed", "logprobs", "grammar", "choices",
+              "prefix", "adapter") + CONTROL_FIELDS + SEQUENCE_FIELDS:
+        if r.get(k):
+            raise ValueError(f"'num_beams' does not go with {k!r}")
+    return checked_beams(cfg.vocab_size, eos, **kw)
 
 
 def _finite(v):
@@ -328,14 +364,39 @@ class GPT2Server:
                                                tlp[b, : new[b]].tolist(), m))
         return res
 
+    def _run_beams(self, reqs, beams, new):
+        """One ragged ``generate(num_beams=...)`` call for requests that share their beam
+        parameters and ``max_new_tokens``: every result carries the best hypothesis as
+        ``"tokens"``, all returned ones as ``"sequences"`` (each cut to its length) and their
+        ``"scores"``."""
+        W, penalty, early, R = beams
+        lens = [len(r["tokens"]) for r in reqs]
+        idx = torch.zeros(len(reqs), max(lens), dtype=torch.long)
+        for b, r in enumerate(reqs):
+            idx[b, : lens[b]] = torch.tensor(r["tokens"], dtype=torch.long)
+        toks, scores, ns = (t.cpu().tolist() for t in self.model.generate(
+            idx.to(self.device), new, lens=lens, eos_token_id=self.eos, num_beams=W,
+            length_penalty=penalty, early_stopping=early, num_return_sequences=R))
+        res = []
+        for b in range(len(reqs)):
+            seqs = [toks[b][j][: ns[b][j]] for j in range(R)]
+            res.append({"tokens": seqs[0], "sequences": seqs,
+                        "scores": [_finite(v) for v in scores[b]]})
+        return res
+
     @batch(max_batch_size=8, batch_wait_timeout_s=0.01)
     async def _generate_batch(self, reqs):
         from ray_amd.ops.functional import LOGPROB_MAX_TOP
 
         results = [None] * len(reqs)
         params, lps, ctls, grs, seqs = {}, {}, {}, {}, {}
+        beams = {}  # (beam parameters, max_new_tokens) -> the requests that share them
         for i, r in enumerate(reqs):
             try:
+                bm = _request_beams(self.model.cfg, r, self.eos)
+                if bm is not None:
+                    beams.setdefault((bm, self._params(r)[1]), []).append(i)
+                    continue
                 lps[i] = _request_logprobs(r, LOGPROB_MAX_TOP)
                 p = self._params(r)
                 ctls[i] = _request_controls(self.model.cfg, r, p[1], None)
@@ -345,6 +406,13 @@ class GPT2Server:
                 params[i] = p
             except Exception as e:  # noqa: BLE001  (one bad request must not fail its batch)
                 results[i] = {"error": f"{type(e).__name__}: {e}"}
+        for (bm, new), members in beams.items():
+            try:
+                for i, res in zip(members, self._run_beams([reqs[i] for i in members], bm, new)):
+                    results[i] = res
+            except ValueError as e:
+                for i in members:
+                    results[i] = {"error": f"ValueError: {e}"}
         if any(p[2] > 0 or reqs[i].get("top_p") is not None or reqs[i].get("seed") is not None
                or lps[i] is not None or ctls[i] or grs[i] is not None or seqs[i]
                for i, p in params.items()):
@@ -620,6 +688,7 @@ class GPT2EngineServer:
         if not isinstance(request, dict):  # HTTP: a JSON body
             request = await request.json()
         try:
+            _request_beams(self.cfg, request, self._eos, enabled=False)
             p = _request_params(self.cfg, self.seed, request)
             _request_logprobs(request, self._logprobs)
             ctl = _request_controls(self.cfg, request, p[1], self._eos, self._logit_processors)
