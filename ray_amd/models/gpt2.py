@@ -658,6 +658,7 @@ class GPT2(nn.Module):
         self.ln_f = LayerNorm(cfg.n_embd, cfg.layer_norm_eps)
         self.lm_head_chunk = 8192  # tokens per fused LM-head/CE chunk
         self.lora = None  # a models.lora.LoRAStack: attach_lora
+        self.w8 = None  # int8 copies of the linears' weights: quantize_weights
         self.reset_parameters()
 
     def reset_parameters(self):
@@ -715,6 +716,43 @@ class GPT2(nn.Module):
                 raise ValueError(f"the adapter stack is {stack.dtype} on {stack.device}, the "
                                  f"model {self.wte.dtype} on {self.wte.device}")
         self.lora = stack
+
+    W8_TARGETS = ("c_attn", "c_proj", "c_fc", "mlp_proj")
+
+    @torch.no_grad()
+    def quantize_weights(self, lm_head=True):
+        """Weight-only int8 for the inference passes (opt-in): keeps ``rf.quantize_w8`` copies
+        ``(q, s)`` of the four linears' weights of every block and, with ``lm_head``, of ``wte``
+        for the tied LM head, in ``self.w8`` (plain attributes on the parameters' device: call
+        it after the model is where it runs). ``prefill*``, ``extend_into``, ``verify_step``,
+        ``decode_step``, ``generate``, ``score`` and the engine then run those linears
+        through ``rf.linear_w8``; LoRA adapters still add on top and the biases stay where
+        they are. The parameters, ``state_dict``, the embedding lookup and the training
+        ``forward`` do not change. Calling it again re-quantises from the current parameters;
+        ``dequantize_weights`` drops the copies."""
+        w8 = {t: [rf.quantize_w8(getattr(blk, t + "_w")) for blk in self.h]
+              for t in self.W8_TARGETS}
+        w8["wte"] = rf.quantize_w8(self.wte) if lm_head else None
+        if self.wte.is_cuda:
+            # the large-M path's scratch at its final size before any step is captured
+            rf.w8_scratch(self.wte.device, max(
+                [self.wte.numel() if lm_head else 0] + [q.numel() for t in self.W8_TARGETS
+                                                        for q, _ in w8[t]]))
+        self.w8 = w8
+        return self
+
+    def dequantize_weights(self):
+        """Drops the int8 copies: the inference passes read the parameters again."""
+        self.w8 = None
+        return self
+
+    def _lm_head_w8(self, h, out=None):
+        """The quantised tied LM head on ``h`` [M, C]: [M, padded_vocab], written into ``out``
+        [M, padded_vocab] when given."""
+        return rf.linear_w8(h, *self.w8["wte"], out=out)
+
+    def _w8_head(self) -> bool:
+        return self.w8 is not None and self.w8["wte"] is not None
 
     def _adapter_ids(self, adapters, B):
         if adapters is None:
@@ -847,10 +885,15 @@ class GPT2(nn.Module):
         h = self._extend(win.clamp(0, cfg.vocab_size - 1), n_win, cache, cache.rows, cache.lens,
                          adapters)
         if out is None:
+            if self._w8_head():
+                return self._lm_head_w8(h)[..., : cfg.vocab_size]
             return F.linear(h, self.wte)[..., : cfg.vocab_size]
         if out.shape != (S, W, cfg.padded_vocab) or not out.is_contiguous():
             raise ValueError(f"out must be a contiguous [{S}, {W}, {cfg.padded_vocab}] tensor")
-        torch.mm(h.reshape(S * W, cfg.n_embd), self.wte.t(), out=out.view(S * W, -1))
+        if self._w8_head():
+            self._lm_head_w8(h.reshape(S * W, cfg.n_embd), out=out.view(S * W, -1))
+        else:
+            torch.mm(h.reshape(S * W, cfg.n_embd), self.wte.t(), out=out.view(S * W, -1))
         return out[..., : cfg.vocab_size]
 
     @staticmethod
@@ -869,14 +912,21 @@ class GPT2(nn.Module):
         ``adapters`` (int32 [B], -1: none): each row's adapter of the attached stack is added
         to the output of the four linears, before the bias where a later kernel adds it."""
         adapters = self._adapter_ids(adapters, x.shape[0])
-        if adapters is None:
-            def linear(i, target, inp, w, b=None):
+        w8 = self.w8
+        if w8 is None:
+            def base(i, target, inp, w, b=None):
                 return F.linear(inp, w, b)
+        else:
+            def base(i, target, inp, w, b=None):  # the int8 copy stands in for w
+                return rf.linear_w8(inp, *w8[target][i], b)
+
+        if adapters is None:
+            linear = base
         else:
             st = self.lora
 
             def linear(i, target, inp, w, b=None):
-                y = F.linear(inp, w, b)
+                y = base(i, target, inp, w, b)
                 rf.lora_add(y, inp, st.a[target][i], st.b[target][i], st.scale, adapters)
                 return y
 
@@ -898,6 +948,8 @@ class GPT2(nn.Module):
         B, T = h.shape[:2]
         last = (n.long() - 1).clamp(0, T - 1)
         hl = h[torch.arange(B, device=h.device), last]
+        if self._w8_head():
+            return self._lm_head_w8(hl)[:, : self.cfg.vocab_size]
         return F.linear(hl, self.wte)[:, : self.cfg.vocab_size]
 
     def _prefill(self, idx, lens, store, adapters=None):
@@ -943,7 +995,9 @@ class GPT2(nn.Module):
             return y.view(B, cfg.n_embd)
 
         h = self._layers(self.wte[tok] + self.wpe[pos], attend, adapters)
-        if out is None:
+        if self._w8_head():
+            logits = self._lm_head_w8(h, out=out)[:, : cfg.vocab_size]
+        elif out is None:
             logits = F.linear(h, self.wte)[:, : cfg.vocab_size]
         else:
             logits = torch.mm(h, self.wte.t(), out=out)[:, : cfg.vocab_size]
@@ -1268,7 +1322,10 @@ class GPT2(nn.Module):
             buf = torch.empty(chunk, cfg.padded_vocab, device=dev, dtype=h.dtype)
             for s in range(0, N, chunk):
                 e = min(N, s + chunk)
-                logits = torch.mm(h[s:e], self.wte.t(), out=buf[: e - s])[:, : cfg.vocab_size]
+                if self._w8_head():
+                    logits = self._lm_head_w8(h[s:e], out=buf[: e - s])[:, : cfg.vocab_size]
+                else:
+                    logits = torch.mm(h[s:e], self.wte.t(), out=buf[: e - s])[:, : cfg.vocab_size]
                 rf.token_logprobs(logits, tok[s:e], top_n, out=out, rows=rows[s:e],
                                   cols=cols[s:e], active=active[s:e])
         return out if top_n else out[0]

@@ -858,6 +858,144 @@ def lora_add(y, x, a_stack, b_stack, scale, idx):
                                  R, NA, stream_ptr()), op)
 
 
+# Largest token count M that linear_w8 gives to the skinny kernel; above it the weight is
+# dequantised into a scratch buffer for the library GEMM (measured: profiles/r21/linear_w8.md).
+W8_SKINNY_MAX_M = 128
+
+_W8_SCRATCH = {}  # device -> flat bf16 buffer, sized for the largest weight seen there
+
+
+def quantize_w8(w):
+    """Symmetric per-output-channel int8 of a weight ``w`` [N, K]: ``(q int8 [N, K], s fp32
+    [N])`` with ``s[n] = absmax(w[n]) / 127`` and ``q = clamp(round_half_even(w / s), -127,
+    127)``, computed in fp32; an all-zero row gives ``s = 0`` and ``q = 0``. Plain torch: it
+    runs once per weight."""
+    if w.dim() != 2 or not w.is_floating_point():
+        raise ValueError(f"quantize_w8: w must be a floating [N, K] tensor, got "
+                         f"{tuple(w.shape)} {w.dtype}")
+    wf = w.detach().float()
+    s = wf.abs().amax(dim=1) / 127.0
+    safe = torch.where(s > 0, s, torch.ones_like(s))
+    q = torch.round(wf / safe[:, None]).clamp_(-127, 127).to(torch.int8)
+    return q.contiguous(), s.contiguous()
+
+
+def _check_w8(op, q, s):
+    if not isinstance(q, torch.Tensor) or q.dim() != 2 or q.dtype != torch.int8:
+        raise ValueError(f"{op}: q must be an int8 [N, K] tensor")
+    if not isinstance(s, torch.Tensor) or s.shape != (q.shape[0],) or \
+            s.dtype != torch.float32 or s.device != q.device:
+        raise ValueError(f"{op}: s must be a float32 tensor of shape [{q.shape[0]}] on "
+                         f"{q.device}")
+
+
+def w8_scratch(device, numel):
+    """The device's dequantisation scratch of ``linear_w8``'s large-M path, at least ``numel``
+    bf16 elements (flat). It grows to the largest weight seen; a caller whose steps are
+    captured in a graph asks for its largest weight first, so the address then stays."""
+    buf = _W8_SCRATCH.get(device)
+    if buf is None or buf.numel() < numel:
+        buf = _W8_SCRATCH[device] = torch.empty(numel, device=device, dtype=torch.bfloat16)
+    return buf
+
+
+def dequant_w8(q, s, out=None):
+    """``w[n, k] = bf16(float(q[n, k]) * s[n])``, [N, K], written into ``out`` (bf16 [N, K],
+    contiguous) when given. HIP kernel (ops/csrc/linear_w8.hip) for contiguous GPU tensors
+    with K % 16 == 0; anything else is ``reference.dequant_w8``."""
+    _check_w8("dequant_w8", q, s)
+    N, K = q.shape
+    if out is not None and (out.shape != (N, K) or out.dtype != torch.bfloat16 or
+                            out.device != q.device or not out.is_contiguous()):
+        raise ValueError(f"dequant_w8: out must be a contiguous bfloat16 [{N}, {K}] tensor on "
+                         f"{q.device}")
+    if not (_hip(q) and K % 16 == 0 and N >= 1):
+        w = ref.dequant_w8(q, s)
+        return w if out is None else out.copy_(w)
+    if out is None:
+        out = torch.empty((N, K), device=q.device, dtype=torch.bfloat16)
+    check(_lib.lib().ra_dequant_w8(ptr(q.contiguous()), ptr(s.contiguous()), ptr(out), N, K,
+                                   stream_ptr()), "dequant_w8")
+    return out
+
+
+def linear_w8(x, q, s, b=None, out=None, splits=None):
+    """Weight-only int8 linear, ``y[..., n] = s[n] * sum_k x[..., k] * q[n, k] + b[n]``: ``x``
+    [..., K], ``q`` int8 [N, K] with per-output-channel scales ``s`` fp32 [N]
+    (``quantize_w8``), ``b`` [N] or None. Returns [..., N] in x's dtype. ``out``: an optional
+    2-D destination of M = prod(leading dims) rows, at least N columns wide (last stride 1,
+    any row stride, e.g. a view of the padded logits buffer); its ``[:, :N]`` is written and
+    returned with x's leading dimensions, the bytes beside it keep their value.
+
+    HIP path (ops/csrc/linear_w8.hip) for bf16 GPU tensors with K % 32 == 0 and N % 32 == 0:
+    fp32 sums, one rounding. M <= ``W8_SKINNY_MAX_M`` takes the skinny MFMA kernel, which
+    reads the int8 weights once and converts them in registers (``splits``: None / 0 automatic,
+    a function of N and K only, or an explicit count); a token's bits there depend on its own
+    row, the weight and (N, K, splits), never on M or the other rows. Larger M dequantises into
+    the device's scratch (``w8_scratch``) and runs the library GEMM on it. One to three
+    launches on the current stream, no host read: capturable. CPU tensors, other dtypes and
+    other shapes use ``reference.linear_w8``. Inference only: raises on tensors that require
+    grad."""
+    op = "linear_w8"
+    _check_w8(op, q, s)
+    N, K = q.shape
+    if not isinstance(x, torch.Tensor) or x.dim() < 1 or x.shape[-1] != K or \
+            x.device != q.device:
+        raise ValueError(f"{op}: x must be [..., {K}] on {q.device}")
+    if b is not None and (b.shape != (N,) or b.dtype != x.dtype or b.device != x.device):
+        raise ValueError(f"{op}: b must be a {x.dtype} tensor of shape [{N}] on {x.device}")
+    if x.requires_grad or (torch.is_grad_enabled() and b is not None and b.requires_grad):
+        raise RuntimeError("linear_w8 is an inference op: run it under torch.no_grad() on "
+                           "tensors that do not require grad")
+    lead = x.shape[:-1]
+    x2 = x.reshape(-1, K)
+    M = x2.shape[0]
+    if out is not None:
+        if out.dim() != 2 or out.shape[0] != M or out.shape[1] < N or out.dtype != x.dtype or \
+                out.device != x.device or (M > 1 and out.stride(0) < N) or out.stride(1) != 1:
+            raise ValueError(f"{op}: out must be a {x.dtype} [{M}, >= {N}] tensor on {x.device} "
+                             f"with unit column stride")
+        out = out[:, :N]
+    if not (_hip(x) and x.dtype == torch.bfloat16 and K % 32 == 0 and N % 32 == 0 and M >= 1):
+        y = ref.linear_w8(x2, q, s, b)
+        if out is not None:
+            y = out.copy_(y)
+        return y.view(*lead, N)
+    S = int(splits or 0)
+    if not 0 <= S <= 64:
+        raise ValueError(f"{op}: splits must be in 0..64")
+    q, s = q.contiguous(), s.contiguous()
+    if q.data_ptr() % 16 or s.data_ptr() % 16:
+        q, s = q.clone(), s.clone()
+    if M > W8_SKINNY_MAX_M:
+        w = dequant_w8(q, s, out=w8_scratch(x.device, N * K)[: N * K].view(N, K))
+        if out is None:
+            return torch.nn.functional.linear(x2, w, b).view(*lead, N)
+        if b is None:
+            torch.mm(x2, w.t(), out=out)
+        else:
+            torch.addmm(b, x2, w.t(), out=out)
+        return out.view(*lead, N) if out.is_contiguous() else out.unflatten(0, lead)
+    if x2.stride(1) != 1 or x2.stride(0) % 8 or (M > 1 and x2.stride(0) < K) or \
+            x2.data_ptr() % 16:
+        x2 = x2.contiguous()
+    if out is None:
+        out = torch.empty((M, N), device=x.device, dtype=torch.bfloat16)
+    ldy = out.stride(0) if M > 1 else N
+    if ldy % 8 or out.data_ptr() % 16:
+        raise ValueError(f"{op}: out needs 16-byte aligned rows (row stride % 8 == 0)")
+    if b is not None:
+        b = b.contiguous()
+        if b.data_ptr() % 16:
+            b = b.clone()
+    L = _lib.lib()
+    nws = L.ra_linear_w8_work(M, N, K, S)
+    ws = torch.empty(nws, device=x.device, dtype=torch.float32) if nws else None
+    check(L.ra_linear_w8(ptr(x2), x2.stride(0) if M > 1 else K, ptr(q), ptr(s), ptr(b), ptr(out),
+                         ldy, ptr(ws), M, N, K, S, stream_ptr()), op)
+    return out.view(*lead, N) if out.is_contiguous() else out.unflatten(0, lead)
+
+
 def slot_advance(tok, lens, n_out, max_new, active, out, eos_token_id=None):
     """The continuous-batching engine's bookkeeping after the sampler, one launch, IN
     PLACE: an active slot with ``n_out[s] < cap`` stores ``out[s, n_out[s]] = tok[s]``,

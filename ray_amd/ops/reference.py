@@ -340,6 +340,19 @@ def lora_add_bmm(y, x, a_stack, b_stack, scale, idx):
     y3.copy_(torch.where(ok, new, y3))
 
 
+def dequant_w8(q, s, dtype=torch.bfloat16):
+    """``w[n, k] = float(q[n, k]) * s[n]`` rounded once to ``dtype`` (ops/csrc/linear_w8.hip)."""
+    return (q.float() * s[:, None]).to(dtype)
+
+
+def linear_w8(x, q, s, b=None):
+    """Weight-only int8 linear (ops/csrc/linear_w8.hip semantics): ``x`` [..., K], ``q`` int8
+    [N, K], ``s`` fp32 [N] per output channel, ``b`` [N] or None.
+    ``y[m, n] = s[n] * sum_k x[m, k] * q[n, k] + b[n]``; the kernel sums in fp32 and rounds
+    once, here it is ``F.linear`` on the weight dequantised to x's dtype."""
+    return F.linear(x, dequant_w8(q, s, x.dtype), b)
+
+
 _MASK64 = (1 << 64) - 1
 
 

@@ -252,9 +252,16 @@ def _logprob_fields(lp, ids, tlp, m):
                              for ri, rv in zip(ids, tlp)]}
 
 
+def _checked_weights(weights):
+    if weights not in (None, "int8"):
+        raise ValueError(f"weights must be None or 'int8', got {weights!r}")
+
+
 class GPT2Server:
     def __init__(self, config="small", state_dict_path=None, seed=0, max_batch_size=8,
-                 batch_wait_timeout_s=0.01, device=None, grammars=None, eos_token_id=None):
+                 batch_wait_timeout_s=0.01, device=None, grammars=None, eos_token_id=None,
+                 weights=None):
+        _checked_weights(weights)
         cfg = getattr(GPT2Config, config)() if isinstance(config, str) else config
         # grammars: name -> TokenDFA (None: the server answers no grammar request); they,
         # and inline choices, end with eos_token_id (default: the first grammar's)
@@ -277,6 +284,8 @@ class GPT2Server:
             model.load_state_dict(torch.load(state_dict_path, map_location="cpu"))
         if self.device.type == "cuda":
             model = model.to(self.device, torch.bfloat16)
+        if weights == "int8":
+            model.quantize_weights()
         self.model = model.eval()
         self.seed = seed
         self._generate_batch.set_max_batch_size(int(max_batch_size))
@@ -515,10 +524,12 @@ class GPT2EngineServer:
                  eos_token_id=None, device=None, poll_every=None, prefixes=None,
                  prefill_chunk=None, adapters=None, lora_rank=16, speculate=0, ngram=(2, 4),
                  logprobs=None, logit_processors=False, grammars=None, grammar_states=0,
-                 sequence_rules=False):
+                 sequence_rules=False, weights=None):
         import queue
         import threading
 
+        _checked_weights(weights)
+        self._weights = weights
         self.cfg = getattr(GPT2Config, config)() if isinstance(config, str) else config
         self.device = _pick_device(device)
         self.seed = seed
@@ -569,6 +580,8 @@ class GPT2EngineServer:
             if self.device.type == "cuda":
                 torch.cuda.set_device(self.device)
                 model = model.to(self.device, torch.bfloat16)
+            if self._weights == "int8":
+                model.quantize_weights()
             kw = {} if poll_every is None else {"poll_every": int(poll_every)}
             if self._adapters:
                 from ray_amd.models.lora import LoRAStack
@@ -765,7 +778,7 @@ def build_gpt2_app(config="small", state_dict_path=None, seed=0, max_batch_size=
                    eos_token_id=None, prefixes=None, prefill_chunk=None, adapters=None,
                    lora_rank=16, speculate=0, ngram=(2, 4), logprobs=None,
                    logit_processors=False, grammars=None, grammar_states=0,
-                   sequence_rules=False):
+                   sequence_rules=False, weights=None):
     """A Serve application around one ``GPT2Server`` replica (``serve.run`` it). ``config``
     names a ``GPT2Config`` preset; without ``state_dict_path`` the weights are the seeded
     random init. ``device`` None: the GPU assigned to the replica, else the CPU.
@@ -795,12 +808,15 @@ def build_gpt2_app(config="small", state_dict_path=None, seed=0, max_batch_size=
     grammars of the requests in flight. ``sequence_rules=True`` (with ``continuous=True``): the
     engine keeps the per-slot tables of ``"stop"``, ``"bad_words"`` and
     ``"no_repeat_ngram_size"``, and a request may name them; the static server needs no option
-    (``"stop"`` needs ``eos_token_id`` on both)."""
+    (``"stop"`` needs ``eos_token_id`` on both). ``weights="int8"`` (both servers): the model
+    runs its linears and LM head on weight-only int8 copies (``GPT2.quantize_weights``), which
+    halves the weight bytes a decode step reads; None keeps the bf16 weights."""
+    _checked_weights(weights)
     if continuous:
         dep = deployment(GPT2EngineServer, name="GPT2EngineServer")
         return dep.bind(config, state_dict_path, seed, slots, eos_token_id, device, None,
                         prefixes, prefill_chunk, adapters, lora_rank, speculate, ngram, logprobs,
-                        logit_processors, grammars, grammar_states, sequence_rules)
+                        logit_processors, grammars, grammar_states, sequence_rules, weights)
     if sequence_rules:
         raise ValueError("sequence_rules needs continuous=True (the static server needs no "
                          "option)")
@@ -809,4 +825,4 @@ def build_gpt2_app(config="small", state_dict_path=None, seed=0, max_batch_size=
                          "continuous=True")
     dep = deployment(GPT2Server, name="GPT2Server")
     return dep.bind(config, state_dict_path, seed, max_batch_size, batch_wait_timeout_s, device,
-                    grammars, eos_token_id)
+                    grammars, eos_token_id, weights)
