@@ -155,17 +155,40 @@ class Block(nn.Module):
 class KVCache:
     """Per-layer K/V of a batch of sequences for ``GPT2.prefill`` / ``decode_step``:
     ``k``, ``v`` [n_layer, B, H, max_len, head_dim] and ``lens`` int32 [B], the positions
-    cached per row (kept on the device: the decode kernel reads it there)."""
+    cached per row (kept on the device: the decode kernel reads it there).
 
-    def __init__(self, cfg: GPT2Config, batch: int, max_len: int, device=None, dtype=None):
+    ``quant="int8"``: ``k`` and ``v`` are int8 and every cached vector has one fp32 scale in
+    ``k_scale`` / ``v_scale`` [n_layer, B, H, max_len] (``rf.attn_decode``'s int8 cache:
+    68 bytes per vector where bf16 takes 128); ``dtype`` is then not used. ``scales(i)`` is
+    layer i's keyword arguments for ``rf.attn_decode`` / ``rf.kv_insert``."""
+
+    def __init__(self, cfg: GPT2Config, batch: int, max_len: int, device=None, dtype=None,
+                 quant=None):
         if max_len < 1 or max_len > cfg.n_positions:
             raise ValueError(f"max_len must be in 1..{cfg.n_positions}, got {max_len}")
+        if quant not in (None, "int8"):
+            raise ValueError(f"quant must be None or 'int8', got {quant!r}")
+        self.quant = quant
         shape = (cfg.n_layer, batch, cfg.n_head, max_len, cfg.n_embd // cfg.n_head)
+        if quant is not None:
+            dtype = torch.int8
+            self.k_scale = torch.zeros(shape[:-1], device=device, dtype=torch.float32)
+            self.v_scale = torch.zeros(shape[:-1], device=device, dtype=torch.float32)
         self.k = torch.zeros(shape, device=device, dtype=dtype)
         self.v = torch.zeros(shape, device=device, dtype=dtype)
         self.lens = torch.zeros(batch, device=device, dtype=torch.int32)
         self.rows = torch.arange(batch, device=device, dtype=torch.int32)  # verify_step's slots
         self.max_len = max_len
+
+    def scales(self, i):
+        if self.quant is None:
+            return {}
+        return {"k_scale": self.k_scale[i], "v_scale": self.v_scale[i]}
+
+    def nbytes(self):
+        """Bytes of K, V and their scales."""
+        ts = (self.k, self.v) + (() if self.quant is None else (self.k_scale, self.v_scale))
+        return sum(t.numel() * t.element_size() for t in ts)
 
 
 class _GraphedStep:
@@ -783,6 +806,9 @@ class GPT2(nn.Module):
         n = min(T, cache.max_len)
 
         def store(i, qkv):
+            if cache.quant is not None:  # one quantiser per device: kv_insert's
+                return rf.kv_insert(qkv, cache.k[i], cache.v[i], cache.rows, lens,
+                                    **cache.scales(i))
             cache.k[i, :, :, :n].copy_(qkv[:, :n, 1].transpose(1, 2))
             cache.v[i, :, :, :n].copy_(qkv[:, :n, 2].transpose(1, 2))
 
@@ -805,7 +831,8 @@ class GPT2(nn.Module):
                              f"{idx.device}")
         lens = torch.as_tensor(lens, device=idx.device).to(torch.int32)
         logits = self._prefill(
-            idx, lens, lambda i, qkv: rf.kv_insert(qkv, cache.k[i], cache.v[i], slots, lens),
+            idx, lens, lambda i, qkv: rf.kv_insert(qkv, cache.k[i], cache.v[i], slots, lens,
+                                                   **cache.scales(i)),
             adapters)
         # kv_insert skips a slot id outside the cache
         self._scatter_lens(cache, slots, (slots >= 0) & (slots < cache.lens.shape[0]), lens)
@@ -846,6 +873,9 @@ class GPT2(nn.Module):
         """The layers of ``extend_into`` / ``verify_step``: the tokens ``idx`` [Bn, Tn] at
         positions ``base[b] + i`` through ``rf.attn_extend`` over rows ``slots`` of ``cache``;
         returns ``ln_f`` of the result, [Bn, Tn, C]. Leaves ``cache.lens`` alone."""
+        if cache.quant is not None:
+            raise ValueError("extend_into / verify_step need rf.attn_extend, which does not "
+                             "serve a quantised KVCache")
         cfg = self.cfg
         Bn, Tn = idx.shape
         H, hd = cfg.n_head, cfg.n_embd // cfg.n_head
@@ -991,7 +1021,8 @@ class GPT2(nn.Module):
         pos = cache.lens.long().clamp(0, cfg.n_positions - 1)
 
         def attend(i, qkv):
-            y = rf.attn_decode(qkv.view(B, 3, H, hd), cache.k[i], cache.v[i], cache.lens)
+            y = rf.attn_decode(qkv.view(B, 3, H, hd), cache.k[i], cache.v[i], cache.lens,
+                               **cache.scales(i))
             return y.view(B, cfg.n_embd)
 
         h = self._layers(self.wte[tok] + self.wpe[pos], attend, adapters)
@@ -1020,7 +1051,8 @@ class GPT2(nn.Module):
                  adapters=None, logprobs=None, repetition_penalty=None, presence_penalty=None,
                  frequency_penalty=None, min_new_tokens=None, logit_bias=None, grammar=None,
                  stop=None, bad_words=None, no_repeat_ngram_size=None, num_beams=None,
-                 length_penalty=1.0, early_stopping=True, num_return_sequences=1):
+                 length_penalty=1.0, early_stopping=True, num_return_sequences=1,
+                 kv_cache=None):
         """Autoregressive generation with a KV cache: ``idx`` [B, T] prompts, right-padded
         to a common length with true lengths ``lens`` (default: all T). Returns the new
         tokens [B, max_new_tokens] (int64). ``temperature`` 0 is greedy, otherwise samples
@@ -1105,9 +1137,21 @@ class GPT2(nn.Module):
         token histories every step, which the per-row history tables of the other controls do
         not follow: ``num_beams`` with ``seeds``, ``generator``, a non-zero ``temperature``,
         ``top_k``, ``top_p``, ``logprobs``, a logit processor, ``grammar`` or a sequence rule
-        is a ``ValueError``. With ``num_beams=None`` not one extra op runs."""
+        is a ``ValueError``. With ``num_beams=None`` not one extra op runs.
+
+        ``kv_cache="int8"`` (None, the default: the cache in the model's dtype): K and V are
+        cached as int8 with one fp32 scale per (row, head, position) vector, 68 bytes where
+        bf16 takes 128 (``KVCache(quant="int8")``); the prompt's K/V are quantised by
+        ``rf.kv_insert`` and every step runs ``rf.attn_decode`` on the int8 cache
+        (ops/csrc/attn_decode_q8.hip), on every sampling path, eager and captured. The logits
+        differ from the bf16 cache's by the quantisation error. Beam search forks cache rows
+        with kernels that do not serve int8: ``num_beams`` with it is a ``ValueError``."""
         cfg = self.cfg
         B, T = idx.shape
+        if kv_cache not in (None, "int8"):
+            raise ValueError(f"kv_cache must be None or 'int8', got {kv_cache!r}")
+        if kv_cache is not None and num_beams is not None:
+            raise ValueError("num_beams does not go with kv_cache")
         if logprobs is not None:
             _checked_top_n("logprobs", logprobs)
         ad = self._adapter_tensor(adapters, B, idx.device)
@@ -1233,7 +1277,7 @@ class GPT2(nn.Module):
             idx_l = idx.tolist()
             rules.put(torch.arange(B, device=dev), rows_s,
                       [idx_l[b][: lens_l[b]] for b in range(B)])
-        cache = KVCache(cfg, B, max(lens_l) + max_new_tokens, dev, self.wte.dtype)
+        cache = KVCache(cfg, B, max(lens_l) + max_new_tokens, dev, self.wte.dtype, kv_cache)
         logits = self.prefill(idx, torch.tensor(lens_l, dtype=torch.int32, device=dev), cache,
                               adapters=ad)
         out = torch.empty(B, max_new_tokens, dtype=torch.long, device=dev)

@@ -163,6 +163,17 @@ prefill, adapters, ``cancel``, logit processors, grammars (``stop`` only: ``bad_
 ``speculate``; a request that names no rule gets the tokens it got before, whoever shares
 the step.
 
+int8 KV cache (``kv_cache="int8"``; None, the default, is the engine without it: not one
+buffer, op or branch on the device differs): the slots' cache is a ``KVCache(quant="int8")``,
+68 bytes per cached vector where bf16 takes 128, so the same memory holds 1.88 times the slots
+or context. Admission quantises the prompts' K/V in ``rf.kv_insert`` and the captured step's
+``decode_step`` runs ``rf.attn_decode`` on the int8 cache (ops/csrc/attn_decode_q8.hip); every
+option that only touches logits (logprobs, logit processors, grammars, sequence rules,
+adapters) works as before. A request's tokens are those of ``generate(..., seeds=[seed],
+kv_cache="int8")`` on it alone. ``prefix_slots``, ``prefill_chunk`` and ``speculate`` need
+``rf.kv_copy`` / ``rf.attn_extend``, which do not serve int8 caches: either with ``kv_cache``
+is a ``ValueError`` at construction.
+
 Single-threaded by contract: every call comes from one thread."""
 
 from __future__ import annotations
@@ -202,7 +213,7 @@ class GPT2Engine:
     def __init__(self, model: GPT2, slots=8, max_len=None, eos_token_id=None, graph=None,
                  poll_every=8, prefix_slots=0, prefill_chunk=None, lora=None, speculate=0,
                  ngram=(2, 4), drafter=None, logprobs=None, logit_processors=False,
-                 grammar_states=0, sequence_rules=False):
+                 grammar_states=0, sequence_rules=False, kv_cache=None):
         cfg = model.cfg
         dev = model.wte.device
         S = int(slots)
@@ -236,6 +247,13 @@ class GPT2Engine:
                              f"{grammar_states!r}")
         if grammar_states and eos_token_id is None:
             raise ValueError("grammar_states needs eos_token_id: a grammar ends with EOS")
+        if kv_cache not in (None, "int8"):
+            raise ValueError(f"kv_cache must be None or 'int8', got {kv_cache!r}")
+        if kv_cache is not None and (int(prefix_slots) or prefill_chunk is not None
+                                     or speculate):
+            # they go through rf.attn_extend / rf.kv_copy, which do not serve int8 caches
+            raise ValueError("kv_cache does not go with prefix_slots, prefill_chunk or "
+                             "speculate")
         if graph is None:
             graph = dev.type == "cuda"
         if graph and dev.type != "cuda":
@@ -247,7 +265,7 @@ class GPT2Engine:
         self.steps = 0  # device steps so far
 
         # everything the captured step reads or writes: allocated once, fixed addresses
-        self.cache = KVCache(cfg, S, self.max_len, dev, model.wte.dtype)
+        self.cache = KVCache(cfg, S, self.max_len, dev, model.wte.dtype, kv_cache)
         self.cache.lens.fill_(rf.SLOT_INACTIVE)
         self.buf = torch.zeros(S, cfg.padded_vocab, device=dev, dtype=model.wte.dtype)
         self.logits = self.buf[:, : cfg.vocab_size]

@@ -124,7 +124,9 @@ _SIGS = {
     "ra_attn_decode_splits": [c_int, c_int, c_int],
     "ra_attn_decode_work": [c_int, c_int, c_int, c_int],
     "ra_attn_decode": [c_void_p] * 6 + [c_int, c_int, c_int, c_float, c_int, c_void_p],
+    "ra_attn_decode_q8": [c_void_p] * 8 + [c_int, c_int, c_int, c_float, c_int, c_void_p],
     "ra_kv_insert": [c_void_p] * 5 + [c_int] * 5 + [c_void_p],
+    "ra_kv_insert_q8": [c_void_p] * 7 + [c_int] * 5 + [c_void_p],
     "ra_kv_copy": [c_void_p] * 7 + [c_int] * 7 + [c_void_p],
     "ra_attn_extend": [c_void_p] * 7 + [c_int] * 5 + [c_float, c_void_p],
     "ra_lora_add": [c_void_p] * 6 + [c_int] * 6 + [c_void_p],

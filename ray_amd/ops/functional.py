@@ -610,7 +610,8 @@ def causal_attention_qkv(qkv, scale=None):
     return y.transpose(1, 2)
 
 
-def attn_decode(qkv_new, k_cache, v_cache, lens, scale=None, splits=None):
+def attn_decode(qkv_new, k_cache, v_cache, lens, scale=None, splits=None, k_scale=None,
+                v_scale=None):
     """One decode step of attention: appends the new token's k/v (``qkv_new`` [B, 3, H, D],
     the packed c_attn output) to ``k_cache`` / ``v_cache`` [B, H, Tmax, D] IN PLACE at
     position ``lens[b]`` and returns the attention of its q over positions 0..lens[b],
@@ -620,7 +621,15 @@ def attn_decode(qkv_new, k_cache, v_cache, lens, scale=None, splits=None):
 
     HIP split-KV kernel for bf16, D == 64 (``splits``: None / 0 automatic, or an explicit
     count); CPU tensors, other dtypes and other head sizes use the plain-torch reference.
-    Inference only: raises on tensors that require grad."""
+    Inference only: raises on tensors that require grad.
+
+    int8 caches take ``k_scale`` / ``v_scale`` (fp32 [B, H, Tmax], contiguous, one scale per
+    cached vector; required with int8 caches, a ``ValueError`` with any other): the new k/v
+    are quantised (``reference.quantize_kv``: ``s = absmax / 127``, round half to even),
+    values and scales are written at position ``lens[b]`` and the attention runs over the
+    dequantised cache, the new position included, so the result is a function of the cache
+    contents. HIP kernel ops/csrc/attn_decode_q8.hip for bf16 ``qkv_new``, D == 64 on the GPU;
+    anything else is the reference."""
     if qkv_new.requires_grad or k_cache.requires_grad or v_cache.requires_grad:
         raise RuntimeError("attn_decode is an inference op: run it under torch.no_grad() on "
                            "tensors that do not require grad")
@@ -632,9 +641,12 @@ def attn_decode(qkv_new, k_cache, v_cache, lens, scale=None, splits=None):
         raise ValueError("attn_decode: caches must be [B, H, Tmax, D] and lens [B]")
     if scale is None:
         scale = D ** -0.5
+    q8 = ref._check_kv_scales("attn_decode", k_cache, v_cache, k_scale, v_scale)
+    if q8 and k_cache.device != qkv_new.device:
+        raise ValueError("attn_decode: qkv_new and the caches must share a device")
     if not (_hip(qkv_new) and qkv_new.dtype == torch.bfloat16 and D == 64
-            and k_cache.dtype == torch.bfloat16 and v_cache.dtype == torch.bfloat16):
-        return ref.attn_decode(qkv_new, k_cache, v_cache, lens, scale)
+            and (q8 or (k_cache.dtype == torch.bfloat16 and v_cache.dtype == torch.bfloat16))):
+        return ref.attn_decode(qkv_new, k_cache, v_cache, lens, scale, k_scale, v_scale)
     if lens.dtype != torch.int32 or not lens.is_cuda:
         raise ValueError("attn_decode: lens must be an int32 tensor on the GPU")
     if not (k_cache.is_contiguous() and v_cache.is_contiguous()):
@@ -647,6 +659,11 @@ def attn_decode(qkv_new, k_cache, v_cache, lens, scale=None, splits=None):
     out = torch.empty((B, H, D), device=qkv_new.device, dtype=torch.bfloat16)
     nws = L.ra_attn_decode_work(B, H, Tmax, S)
     ws = torch.empty(nws, device=qkv_new.device, dtype=torch.float32) if nws else None
+    if q8:
+        check(L.ra_attn_decode_q8(ptr(qkv_new), ptr(k_cache), ptr(v_cache), ptr(k_scale),
+                                  ptr(v_scale), ptr(lens), ptr(out), ptr(ws), B, H, Tmax,
+                                  float(scale), S, stream_ptr()), "attn_decode_q8")
+        return out
     check(L.ra_attn_decode(ptr(qkv_new), ptr(k_cache), ptr(v_cache), ptr(lens), ptr(out), ptr(ws),
                            B, H, Tmax, float(scale), S, stream_ptr()), "attn_decode")
     return out
@@ -659,6 +676,12 @@ def _int_vec(name, op, t, n, like, dtype=torch.int32):
     if not isinstance(t, torch.Tensor) or t.shape != (n,) or t.dtype != dtype or \
             t.device != like.device:
         raise ValueError(f"{op}: {name} must be a {dtype} tensor of shape [{n}] on {like.device}")
+
+
+def _no_int8_cache(op, cache):
+    if cache.dtype == torch.int8:
+        raise ValueError(f"{op}: int8 K/V caches are served by attn_decode and kv_insert only "
+                         f"(their bytes mean nothing without the scales)")
 
 
 def _check_qkv_caches(op, qkv, k_cache, v_cache):
@@ -679,7 +702,7 @@ def _check_qkv_caches(op, qkv, k_cache, v_cache):
     return Bn, T, H, D, S, Tmax
 
 
-def kv_insert(qkv, k_cache, v_cache, slots, lens):
+def kv_insert(qkv, k_cache, v_cache, slots, lens, k_scale=None, v_scale=None):
     """Moves one layer's prefill K/V (``qkv`` [Bn, Tp, 3, H, D], the packed c_attn output
     of the right-padded prompts) into slots of a wider cache: for every row b with
     0 <= slots[b] < S, ``k_cache[slots[b], h, t] = qkv[b, t, 1, h]`` (V: index 2) for t in
@@ -689,16 +712,28 @@ def kv_insert(qkv, k_cache, v_cache, slots, lens):
     length skips the work. Two rows naming one slot are the caller's error.
 
     HIP kernel for bf16, D == 64 GPU tensors; CPU tensors, other dtypes and other head
-    sizes use the plain-torch reference."""
+    sizes use the plain-torch reference.
+
+    int8 caches take ``k_scale`` / ``v_scale`` (fp32 [S, H, Tmax], contiguous; required with
+    int8 caches, a ``ValueError`` with any other): every moved vector is quantised as in
+    ``attn_decode`` and its scale written beside it, in one launch for K and V
+    (ops/csrc/attn_decode_q8.hip), with the same checks and skips."""
     Bn, Tp, H, D, S, Tmax = _check_qkv_caches("kv_insert", qkv, k_cache, v_cache)
     _int_vec("slots", "kv_insert", slots, Bn, qkv)
     _int_vec("lens", "kv_insert", lens, Bn, qkv)
+    q8 = ref._check_kv_scales("kv_insert", k_cache, v_cache, k_scale, v_scale)
     if not (_hip(qkv) and qkv.dtype == torch.bfloat16 and D == 64
-            and k_cache.dtype == torch.bfloat16):
-        return ref.kv_insert(qkv, k_cache, v_cache, slots, lens)
+            and (q8 or k_cache.dtype == torch.bfloat16)):
+        return ref.kv_insert(qkv, k_cache, v_cache, slots, lens, k_scale, v_scale)
     if not (k_cache.is_contiguous() and v_cache.is_contiguous()):
         raise ValueError("kv_insert: the caches are written in place and must be contiguous")
     qkv = qkv.contiguous()
+    if q8:
+        check(_lib.lib().ra_kv_insert_q8(ptr(qkv), ptr(k_cache), ptr(v_cache), ptr(k_scale),
+                                         ptr(v_scale), ptr(slots.contiguous()),
+                                         ptr(lens.contiguous()), Bn, Tp, H, S, Tmax,
+                                         stream_ptr()), "kv_insert_q8")
+        return
     check(_lib.lib().ra_kv_insert(ptr(qkv), ptr(k_cache), ptr(v_cache), ptr(slots.contiguous()),
                                   ptr(lens.contiguous()), Bn, Tp, H, S, Tmax, stream_ptr()),
           "kv_insert")
@@ -726,6 +761,7 @@ def attn_extend(qkv_new, k_cache, v_cache, slots, base, n_new, scale=None):
         raise RuntimeError("attn_extend is an inference op: run it under torch.no_grad() on "
                            "tensors that do not require grad")
     Bn, Tn, H, D, S, Tmax = _check_qkv_caches("attn_extend", qkv_new, k_cache, v_cache)
+    _no_int8_cache("attn_extend", k_cache)
     for name, t in (("slots", slots), ("base", base), ("n_new", n_new)):
         _int_vec(name, "attn_extend", t, Bn, qkv_new)
     if scale is None:
@@ -773,6 +809,7 @@ def kv_copy(src_k, src_v, dst_k, dst_v, src_rows, dst_rows, lens):
     if len({t.dtype for t in (src_k, src_v, dst_k, dst_v)}) != 1 or \
             len({t.device for t in (src_k, src_v, dst_k, dst_v)}) != 1:
         raise ValueError("kv_copy: the four caches must share a dtype and a device")
+    _no_int8_cache("kv_copy", src_k)
     if not isinstance(src_rows, torch.Tensor) or src_rows.dim() != 1 or src_rows.shape[0] < 1:
         raise ValueError("kv_copy: src_rows must be an int32 tensor of shape [Bn]")
     Bn = src_rows.shape[0]
@@ -1784,6 +1821,7 @@ def beam_kv_fork(k, v, parent, lens):
             raise ValueError(f"{op}: {name} must be [L, S, H, Tmax, D]")
     if k.shape != v.shape or k.dtype != v.dtype or k.device != v.device or min(k.shape) < 1:
         raise ValueError(f"{op}: k and v must be non-empty and share a shape, a dtype and a device")
+    _no_int8_cache(op, k)
     Ln, S, H, Tmax, D = k.shape
     _int_vec("parent", op, parent, S, k)
     _int_vec("lens", op, lens, S, k)

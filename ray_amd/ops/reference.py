@@ -38,39 +38,87 @@ def cross_entropy(logits, targets, vocab_size=None, ignore_index=-100):
     return F.cross_entropy(lf, targets.reshape(-1), ignore_index=ignore_index)
 
 
-def attn_decode(qkv_new, k_cache, v_cache, lens, scale=None):
+def quantize_kv(x):
+    """The int8 K/V cache's quantiser on the vectors ``x`` [..., D], in fp32: ``(q int8 [..., D],
+    s fp32 [...])`` with ``s = absmax(x) / 127`` and ``q = clamp(round_half_even(x / s), -127,
+    127)``; an all-zero vector gives ``s = 0`` and ``q = 0`` (``quantize_w8``'s rule per
+    vector). Both quotients are true divisions between tensors: a Python-scalar divisor would
+    let the GPU multiply by a rounded reciprocal."""
+    xf = x.float()
+    amax = xf.abs().amax(-1)
+    s = amax / torch.full_like(amax, 127.0)
+    safe = torch.where(s > 0, s, torch.ones_like(s))
+    q = torch.round(xf / safe.unsqueeze(-1)).clamp_(-127, 127).to(torch.int8)
+    return q, s
+
+
+def _check_kv_scales(op, k_cache, v_cache, k_scale, v_scale):
+    """True for an int8 cache with its two scale tensors (fp32, the caches' shape without
+    the last dimension, contiguous, on their device), False for a plain cache without;
+    anything between is a ``ValueError``."""
+    q8 = k_cache.dtype == torch.int8 or v_cache.dtype == torch.int8
+    if not q8:
+        if k_scale is not None or v_scale is not None:
+            raise ValueError(f"{op}: k_scale / v_scale go with int8 caches only")
+        return False
+    if k_cache.dtype != v_cache.dtype:
+        raise ValueError(f"{op}: the caches must share a dtype")
+    for name, t in (("k_scale", k_scale), ("v_scale", v_scale)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or \
+                t.shape != k_cache.shape[:-1] or t.device != k_cache.device or \
+                not t.is_contiguous():
+            raise ValueError(f"{op}: int8 caches need {name}, a contiguous float32 tensor of "
+                             f"shape {list(k_cache.shape[:-1])} on {k_cache.device}")
+    return True
+
+
+def attn_decode(qkv_new, k_cache, v_cache, lens, scale=None, k_scale=None, v_scale=None):
     """Single-query attention over a K/V cache (ops/csrc/attn_decode.hip semantics).
 
     ``qkv_new`` [B, 3, H, D] is the new token's packed q/k/v, the caches are
     [B, H, Tmax, D], ``lens`` [B] the cached positions per row. A row with
     0 <= lens[b] < Tmax gets k/v written IN PLACE at position lens[b] and attends over
     0..lens[b]; any other row is inactive (cache untouched, zero output). Positions past
-    lens[b] are masked out whatever they hold (NaN included). fp32 math, no host sync."""
+    lens[b] are masked out whatever they hold (NaN included). fp32 math, no host sync.
+
+    int8 caches with ``k_scale`` / ``v_scale`` fp32 [B, H, Tmax]
+    (ops/csrc/attn_decode_q8.hip semantics): the new k/v are quantised (``quantize_kv``),
+    values and scales are written at position lens[b], and the attention runs over the
+    dequantised cache ``float(q) * s``, the new position included."""
     B, _, H, D = qkv_new.shape
     Tmax = k_cache.shape[2]
     if scale is None:
         scale = D ** -0.5
+    q8 = _check_kv_scales("attn_decode", k_cache, v_cache, k_scale, v_scale)
     q, k, v = qkv_new.unbind(1)
     lens = lens.long()
     active = (lens >= 0) & (lens < Tmax)
     idx = lens.clamp(0, Tmax - 1).view(B, 1, 1, 1).expand(B, H, 1, D)
     act = active.view(B, 1, 1, 1)
-    for cache, new in ((k_cache, k), (v_cache, v)):
+    for cache, sc, new in ((k_cache, k_scale, k), (v_cache, v_scale, v)):
+        if q8:
+            new, s = quantize_kv(new)
+            i1 = idx[..., 0]
+            sc.scatter_(2, i1, torch.where(act[..., 0], s.unsqueeze(2), sc.gather(2, i1)))
         cache.scatter_(2, idx, torch.where(act, new.unsqueeze(2).to(cache.dtype),
                                            cache.gather(2, idx)))
     t = torch.arange(Tmax, device=lens.device)
     keep = ((t.view(1, 1, Tmax) <= lens.view(B, 1, 1)) & active.view(B, 1, 1)).expand(B, H, Tmax)
-    s = (q.float().unsqueeze(2) @ k_cache.float().transpose(-1, -2)).squeeze(2) * scale
+    kf, vf = k_cache.float(), v_cache.float()
+    if q8:  # (masked positions may hold NaN scales: they are masked after the product)
+        kf, vf = kf * k_scale.unsqueeze(-1), vf * v_scale.unsqueeze(-1)
+        kf = torch.where(keep.unsqueeze(-1), kf, torch.zeros((), device=kf.device))
+    s = (q.float().unsqueeze(2) @ kf.transpose(-1, -2)).squeeze(2) * scale
     p = torch.softmax(s.masked_fill(~keep, float("-inf")), -1)
     p = torch.where(keep, p, torch.zeros_like(p))  # inactive rows: softmax of all -inf
-    vf = torch.where(keep.unsqueeze(-1), v_cache.float(), torch.zeros((), device=s.device))
+    vf = torch.where(keep.unsqueeze(-1), vf, torch.zeros((), device=s.device))
     return (p.unsqueeze(2) @ vf).squeeze(2).to(qkv_new.dtype)
 
 
 SLOT_INACTIVE = -(1 << 30)  # ops/csrc/kv_slots.hip kSlotInactive: an idle slot's cache.lens
 
 
-def kv_insert(qkv, k_cache, v_cache, slots, lens):
+def kv_insert(qkv, k_cache, v_cache, slots, lens, k_scale=None, v_scale=None):
     """Moves a prefill's K/V into slots of a wider cache (ops/csrc/kv_slots.hip semantics).
 
     ``qkv`` [Bn, Tp, 3, H, D] is one layer's packed c_attn output for the right-padded
@@ -78,9 +126,13 @@ def kv_insert(qkv, k_cache, v_cache, slots, lens):
     row b with 0 <= slots[b] < S, t in [0, min(lens[b], Tp, Tmax)) and every h,
     ``k_cache[slots[b], h, t] = qkv[b, t, 1, h]`` and the same for V with index 2, IN PLACE;
     every other element keeps its bits. Two rows naming one slot are the caller's error.
-    No host sync."""
+    No host sync.
+
+    int8 caches with ``k_scale`` / ``v_scale`` fp32 [S, H, Tmax]: every moved vector is
+    quantised (``quantize_kv``) and its scale written beside it; nothing else is written."""
     Bn, Tp, _, H, D = qkv.shape
     S, Tmax = k_cache.shape[0], k_cache.shape[2]
+    q8 = _check_kv_scales("kv_insert", k_cache, v_cache, k_scale, v_scale)
     dev = qkv.device
     n = min(Tp, Tmax)
     slots = slots.long()
@@ -93,9 +145,12 @@ def kv_insert(qkv, k_cache, v_cache, slots, lens):
     row = row.clamp(max=Bn - 1)
     t = torch.arange(n, device=dev)
     take = (fed.view(S, 1) & (t.view(1, n) < lens.long()[row].view(S, 1))).view(S, 1, n, 1)
-    for cache, which in ((k_cache, 1), (v_cache, 2)):
-        new = qkv[row, :n, which].transpose(1, 2).to(cache.dtype)  # [S, H, n, D]
-        cache[:, :, :n] = torch.where(take, new, cache[:, :, :n])
+    for cache, sc, which in ((k_cache, k_scale, 1), (v_cache, v_scale, 2)):
+        new = qkv[row, :n, which].transpose(1, 2)  # [S, H, n, D]
+        if q8:
+            new, s = quantize_kv(new)
+            sc[:, :, :n] = torch.where(take[..., 0], s, sc[:, :, :n])
+        cache[:, :, :n] = torch.where(take, new.to(cache.dtype), cache[:, :, :n])
 
 
 def _slot_rows(slots, valid, S, Bn):

@@ -257,11 +257,19 @@ def _checked_weights(weights):
         raise ValueError(f"weights must be None or 'int8', got {weights!r}")
 
 
+def _checked_kv_cache(kv_cache):
+    if kv_cache not in (None, "int8"):
+        raise ValueError(f"kv_cache must be None or 'int8', got {kv_cache!r}")
+
+
 class GPT2Server:
     def __init__(self, config="small", state_dict_path=None, seed=0, max_batch_size=8,
                  batch_wait_timeout_s=0.01, device=None, grammars=None, eos_token_id=None,
-                 weights=None):
+                 weights=None, kv_cache=None):
         _checked_weights(weights)
+        _checked_kv_cache(kv_cache)
+        # (generate's keyword only when asked for: the call is otherwise what it was)
+        self._kv = {} if kv_cache is None else {"kv_cache": kv_cache}
         cfg = getattr(GPT2Config, config)() if isinstance(config, str) else config
         # grammars: name -> TokenDFA (None: the server answers no grammar request); they,
         # and inline choices, end with eos_token_id (default: the first grammar's)
@@ -303,7 +311,8 @@ class GPT2Server:
         if temp > 0:
             gen = torch.Generator(device=self.device).manual_seed(self.seed)
         out = self.model.generate(idx.to(self.device), max(new), lens=lens, temperature=temp,
-                                  top_k=reqs[0].get("top_k"), generator=gen).cpu()
+                                  top_k=reqs[0].get("top_k"), generator=gen,
+                                  **self._kv).cpu()
         return [out[b, : new[b]].tolist() for b in range(len(reqs))]
 
     def _params(self, r):
@@ -330,7 +339,7 @@ class GPT2Server:
         for b, r in enumerate(reqs):
             idx[b, : lens[b]] = torch.tensor(r["tokens"], dtype=torch.long)
         kw = dict(lens=lens, temperature=[p[2] for p in params], top_k=[p[3] for p in params],
-                  top_p=[p[4] for p in params], seeds=[p[5] for p in params])
+                  top_p=[p[4] for p in params], seeds=[p[5] for p in params], **self._kv)
         if ctls is not None and any(ctls):
             # min_new_tokens is checked against the request's own max_new_tokens, above
             for k in CONTROL_FIELDS:
@@ -385,7 +394,7 @@ class GPT2Server:
             idx[b, : lens[b]] = torch.tensor(r["tokens"], dtype=torch.long)
         toks, scores, ns = (t.cpu().tolist() for t in self.model.generate(
             idx.to(self.device), new, lens=lens, eos_token_id=self.eos, num_beams=W,
-            length_penalty=penalty, early_stopping=early, num_return_sequences=R))
+            length_penalty=penalty, early_stopping=early, num_return_sequences=R, **self._kv))
         res = []
         for b in range(len(reqs)):
             seqs = [toks[b][j][: ns[b][j]] for j in range(R)]
@@ -524,12 +533,14 @@ class GPT2EngineServer:
                  eos_token_id=None, device=None, poll_every=None, prefixes=None,
                  prefill_chunk=None, adapters=None, lora_rank=16, speculate=0, ngram=(2, 4),
                  logprobs=None, logit_processors=False, grammars=None, grammar_states=0,
-                 sequence_rules=False, weights=None):
+                 sequence_rules=False, weights=None, kv_cache=None):
         import queue
         import threading
 
         _checked_weights(weights)
+        _checked_kv_cache(kv_cache)
         self._weights = weights
+        self._kv_cache = kv_cache
         self.cfg = getattr(GPT2Config, config)() if isinstance(config, str) else config
         self.device = _pick_device(device)
         self.seed = seed
@@ -594,7 +605,8 @@ class GPT2EngineServer:
                              ngram=self._ngram, logprobs=self._logprobs,
                              logit_processors=self._logit_processors,
                              grammar_states=self._grammar_states,
-                             sequence_rules=self._sequence_rules, **kw)
+                             sequence_rules=self._sequence_rules,
+                             kv_cache=self._kv_cache, **kw)
             for name, dfa in (self._grammars or {}).items():
                 try:
                     self._gids[name] = eng.add_grammar(dfa)
@@ -778,7 +790,7 @@ def build_gpt2_app(config="small", state_dict_path=None, seed=0, max_batch_size=
                    eos_token_id=None, prefixes=None, prefill_chunk=None, adapters=None,
                    lora_rank=16, speculate=0, ngram=(2, 4), logprobs=None,
                    logit_processors=False, grammars=None, grammar_states=0,
-                   sequence_rules=False, weights=None):
+                   sequence_rules=False, weights=None, kv_cache=None):
     """A Serve application around one ``GPT2Server`` replica (``serve.run`` it). ``config``
     names a ``GPT2Config`` preset; without ``state_dict_path`` the weights are the seeded
     random init. ``device`` None: the GPU assigned to the replica, else the CPU.
@@ -810,13 +822,20 @@ def build_gpt2_app(config="small", state_dict_path=None, seed=0, max_batch_size=
     ``"no_repeat_ngram_size"``, and a request may name them; the static server needs no option
     (``"stop"`` needs ``eos_token_id`` on both). ``weights="int8"`` (both servers): the model
     runs its linears and LM head on weight-only int8 copies (``GPT2.quantize_weights``), which
-    halves the weight bytes a decode step reads; None keeps the bf16 weights."""
+    halves the weight bytes a decode step reads; None keeps the bf16 weights.
+    ``kv_cache="int8"`` (both servers; composes with ``weights``): K and V are cached as int8
+    with one fp32 scale per vector, 0.53x the cache bytes (``generate(kv_cache=)`` /
+    ``GPT2Engine(kv_cache=)``); with ``continuous=True`` it does not go with ``prefixes``,
+    ``prefill_chunk`` or ``speculate``, and the static server answers no beam-search request
+    with it. None keeps the cache in the model's dtype."""
     _checked_weights(weights)
+    _checked_kv_cache(kv_cache)
     if continuous:
         dep = deployment(GPT2EngineServer, name="GPT2EngineServer")
         return dep.bind(config, state_dict_path, seed, slots, eos_token_id, device, None,
                         prefixes, prefill_chunk, adapters, lora_rank, speculate, ngram, logprobs,
-                        logit_processors, grammars, grammar_states, sequence_rules, weights)
+                        logit_processors, grammars, grammar_states, sequence_rules, weights,
+                        kv_cache)
     if sequence_rules:
         raise ValueError("sequence_rules needs continuous=True (the static server needs no "
                          "option)")
@@ -825,4 +844,4 @@ def build_gpt2_app(config="small", state_dict_path=None, seed=0, max_batch_size=
                          "continuous=True")
     dep = deployment(GPT2Server, name="GPT2Server")
     return dep.bind(config, state_dict_path, seed, max_batch_size, batch_wait_timeout_s, device,
-                    grammars, eos_token_id, weights)
+                    grammars, eos_token_id, weights, kv_cache)
