@@ -681,7 +681,7 @@ class GPT2(nn.Module):
         self.ln_f = LayerNorm(cfg.n_embd, cfg.layer_norm_eps)
         self.lm_head_chunk = 8192  # tokens per fused LM-head/CE chunk
         self.lora = None  # a models.lora.LoRAStack: attach_lora
-        self.w8 = None  # int8 copies of the linears' weights: quantize_weights
+        self.w8 = None  # int8 or MXFP4 copies of the linears' weights: quantize_weights
         self.reset_parameters()
 
     def reset_parameters(self):
@@ -743,36 +743,48 @@ class GPT2(nn.Module):
     W8_TARGETS = ("c_attn", "c_proj", "c_fc", "mlp_proj")
 
     @torch.no_grad()
-    def quantize_weights(self, lm_head=True):
-        """Weight-only int8 for the inference passes (opt-in): keeps ``rf.quantize_w8`` copies
+    def quantize_weights(self, lm_head=True, fmt="int8"):
+        """Weight-only quantisation for the inference passes (opt-in): keeps quantised copies
         ``(q, s)`` of the four linears' weights of every block and, with ``lm_head``, of ``wte``
         for the tied LM head, in ``self.w8`` (plain attributes on the parameters' device: call
-        it after the model is where it runs). ``prefill*``, ``extend_into``, ``verify_step``,
-        ``decode_step``, ``generate``, ``score`` and the engine then run those linears
-        through ``rf.linear_w8``; LoRA adapters still add on top and the biases stay where
-        they are. The parameters, ``state_dict``, the embedding lookup and the training
-        ``forward`` do not change. Calling it again re-quantises from the current parameters;
-        ``dequantize_weights`` drops the copies."""
-        w8 = {t: [rf.quantize_w8(getattr(blk, t + "_w")) for blk in self.h]
+        it after the model is where it runs). ``fmt="int8"``: ``rf.quantize_w8`` pairs (int8,
+        fp32 per-channel scales) run by ``rf.linear_w8``; ``fmt="mxfp4"``: ``rf.quantize_w4``
+        pairs (uint8 e2m1 nibbles, uint8 e8m0 block scales; needs n_embd % 32 == 0) run by
+        ``rf.linear_w4``. ``prefill*``, ``extend_into``, ``verify_step``, ``decode_step``,
+        ``generate``, ``score`` and the engine then run those linears on the copies; LoRA
+        adapters still add on top and the biases stay where they are. The parameters,
+        ``state_dict``, the embedding lookup and the training ``forward`` do not change.
+        Calling it again re-quantises from the current parameters; ``dequantize_weights``
+        drops the copies."""
+        if fmt not in ("int8", "mxfp4"):
+            raise ValueError(f"fmt must be 'int8' or 'mxfp4', got {fmt!r}")
+        quantize = rf.quantize_w8 if fmt == "int8" else rf.quantize_w4
+        w8 = {t: [quantize(getattr(blk, t + "_w")) for blk in self.h]
               for t in self.W8_TARGETS}
-        w8["wte"] = rf.quantize_w8(self.wte) if lm_head else None
+        w8["wte"] = quantize(self.wte) if lm_head else None
         if self.wte.is_cuda:
             # the large-M path's scratch at its final size before any step is captured
             rf.w8_scratch(self.wte.device, max(
-                [self.wte.numel() if lm_head else 0] + [q.numel() for t in self.W8_TARGETS
-                                                        for q, _ in w8[t]]))
+                [self.wte.numel() if lm_head else 0] +
+                [getattr(blk, t + "_w").numel() for t in self.W8_TARGETS for blk in self.h]))
         self.w8 = w8
         return self
 
     def dequantize_weights(self):
-        """Drops the int8 copies: the inference passes read the parameters again."""
+        """Drops the quantised copies: the inference passes read the parameters again."""
         self.w8 = None
         return self
+
+    @staticmethod
+    def _linear_q(inp, q, s, b=None, out=None):
+        """The quantised linear of a ``w8`` pair: int8 ``q`` is per-channel int8, uint8 MXFP4."""
+        op = rf.linear_w8 if q.dtype == torch.int8 else rf.linear_w4
+        return op(inp, q, s, b, out=out)
 
     def _lm_head_w8(self, h, out=None):
         """The quantised tied LM head on ``h`` [M, C]: [M, padded_vocab], written into ``out``
         [M, padded_vocab] when given."""
-        return rf.linear_w8(h, *self.w8["wte"], out=out)
+        return self._linear_q(h, *self.w8["wte"], out=out)
 
     def _w8_head(self) -> bool:
         return self.w8 is not None and self.w8["wte"] is not None
@@ -947,8 +959,8 @@ class GPT2(nn.Module):
             def base(i, target, inp, w, b=None):
                 return F.linear(inp, w, b)
         else:
-            def base(i, target, inp, w, b=None):  # the int8 copy stands in for w
-                return rf.linear_w8(inp, *w8[target][i], b)
+            def base(i, target, inp, w, b=None):  # the quantised copy stands in for w
+                return self._linear_q(inp, *w8[target][i], b)
 
         if adapters is None:
             linear = base

@@ -135,6 +135,11 @@ _SIGS = {
     "ra_linear_w8": [c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p,
                      c_int, c_int, c_int, c_int, c_void_p],
     "ra_dequant_w8": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p],
+    "ra_linear_w4_splits": [c_int, c_int],
+    "ra_linear_w4_work": [c_int, c_int, c_int, c_int],
+    "ra_linear_w4": [c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p,
+                     c_int, c_int, c_int, c_int, c_void_p],
+    "ra_dequant_w4": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p],
     "ra_slot_advance": [c_void_p] * 6 + [c_int, c_int, c_long, c_void_p],
     "ra_spec_draft": [c_void_p] * 8 + [c_int] * 5 + [c_void_p],
     "ra_spec_accept": [c_void_p] * 13 + [c_int] * 4 + [c_long, c_void_p],

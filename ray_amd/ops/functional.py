@@ -1033,6 +1033,125 @@ def linear_w8(x, q, s, b=None, out=None, splits=None):
     return out.view(*lead, N) if out.is_contiguous() else out.unflatten(0, lead)
 
 
+# Largest token count M that linear_w4 gives to the skinny kernel; above it the weight is
+# dequantised into the scratch buffer for the library GEMM (profiles/r23/linear_w4.md).
+W4_SKINNY_MAX_M = 128
+
+quantize_w4 = ref.quantize_w4
+
+
+def _check_w4(op, q, s):
+    if not isinstance(q, torch.Tensor) or q.dim() != 2 or q.dtype != torch.uint8 or \
+            q.shape[1] % 16 or q.shape[1] == 0:
+        raise ValueError(f"{op}: q must be a uint8 [N, K/2] tensor with K % 32 == 0")
+    want = (q.shape[0], q.shape[1] // 16)
+    if not isinstance(s, torch.Tensor) or s.shape != want or s.dtype != torch.uint8 or \
+            s.device != q.device:
+        raise ValueError(f"{op}: s must be a uint8 tensor of shape {list(want)} on {q.device}")
+
+
+def dequant_w4(q, s, out=None):
+    """``w[n, k] = bf16(e2m1(q) * 2^(s[n, k // 32] - 127))``, [N, K], for MXFP4 weights ``q``
+    uint8 [N, K/2], ``s`` uint8 [N, K/32] (``quantize_w4``); written into ``out`` (bf16 [N, K],
+    contiguous) when given. HIP kernel (ops/csrc/linear_w4.hip) for GPU tensors; CPU tensors
+    use ``reference.dequant_w4``."""
+    _check_w4("dequant_w4", q, s)
+    N, K = q.shape[0], 2 * q.shape[1]
+    if out is not None and (out.shape != (N, K) or out.dtype != torch.bfloat16 or
+                            out.device != q.device or not out.is_contiguous()):
+        raise ValueError(f"dequant_w4: out must be a contiguous bfloat16 [{N}, {K}] tensor on "
+                         f"{q.device}")
+    if not (_hip(q) and N >= 1):
+        w = ref.dequant_w4(q, s)
+        return w if out is None else out.copy_(w)
+    if out is None:
+        out = torch.empty((N, K), device=q.device, dtype=torch.bfloat16)
+    q = q.contiguous()
+    if q.data_ptr() % 16:
+        q = q.clone()
+    check(_lib.lib().ra_dequant_w4(ptr(q), ptr(s.contiguous()), ptr(out), N, K, stream_ptr()),
+          "dequant_w4")
+    return out
+
+
+def linear_w4(x, q, s, b=None, out=None, splits=None):
+    """Weight-only MXFP4 linear, ``y[..., n] = sum_k x[..., k] * dq[n, k] + b[n]`` with
+    ``dq = e2m1(q) * 2^(s - 127)``: ``x`` [..., K], ``q`` uint8 [N, K/2] with one e8m0 scale
+    byte per 32 consecutive k in ``s`` uint8 [N, K/32] (``quantize_w4``), ``b`` [N] or None.
+    Returns [..., N] in x's dtype. ``out``: an optional 2-D destination of M = prod(leading
+    dims) rows, at least N columns wide (last stride 1, any row stride, e.g. a view of the
+    padded logits buffer); its ``[:, :N]`` is written and returned with x's leading dimensions,
+    the bytes beside it keep their value.
+
+    HIP path (ops/csrc/linear_w4.hip) for bf16 GPU tensors with K % 64 == 0 and N % 32 == 0:
+    exact bf16 operands, fp32 sums, one rounding. M <= ``W4_SKINNY_MAX_M`` takes the skinny
+    MFMA kernel, which reads the 4-bit weights once and converts them in registers
+    (``splits``: None / 0 automatic, a function of N and K only, or an explicit count); a
+    token's bits there depend on its own row, the weight and (N, K, splits), never on M or the
+    other rows. Larger M dequantises into the device's scratch (``w8_scratch``) and runs the
+    library GEMM on it. One to three launches on the current stream, no host read: capturable.
+    CPU tensors, other dtypes and other shapes use ``reference.linear_w4``. Inference only:
+    raises on tensors that require grad."""
+    op = "linear_w4"
+    _check_w4(op, q, s)
+    N, K = q.shape[0], 2 * q.shape[1]
+    if not isinstance(x, torch.Tensor) or x.dim() < 1 or x.shape[-1] != K or \
+            x.device != q.device:
+        raise ValueError(f"{op}: x must be [..., {K}] on {q.device}")
+    if b is not None and (b.shape != (N,) or b.dtype != x.dtype or b.device != x.device):
+        raise ValueError(f"{op}: b must be a {x.dtype} tensor of shape [{N}] on {x.device}")
+    if x.requires_grad or (torch.is_grad_enabled() and b is not None and b.requires_grad):
+        raise RuntimeError("linear_w4 is an inference op: run it under torch.no_grad() on "
+                           "tensors that do not require grad")
+    lead = x.shape[:-1]
+    x2 = x.reshape(-1, K)
+    M = x2.shape[0]
+    if out is not None:
+        if out.dim() != 2 or out.shape[0] != M or out.shape[1] < N or out.dtype != x.dtype or \
+                out.device != x.device or (M > 1 and out.stride(0) < N) or out.stride(1) != 1:
+            raise ValueError(f"{op}: out must be a {x.dtype} [{M}, >= {N}] tensor on {x.device} "
+                             f"with unit column stride")
+        out = out[:, :N]
+    if not (_hip(x) and x.dtype == torch.bfloat16 and K % 64 == 0 and N % 32 == 0 and M >= 1):
+        y = ref.linear_w4(x2, q, s, b)
+        if out is not None:
+            y = out.copy_(y)
+        return y.view(*lead, N)
+    S = int(splits or 0)
+    if not 0 <= S <= 64:
+        raise ValueError(f"{op}: splits must be in 0..64")
+    q, s = q.contiguous(), s.contiguous()
+    if q.data_ptr() % 16 or s.data_ptr() % 2:
+        q, s = q.clone(), s.clone()
+    if M > W4_SKINNY_MAX_M:
+        w = dequant_w4(q, s, out=w8_scratch(x.device, N * K)[: N * K].view(N, K))
+        if out is None:
+            return torch.nn.functional.linear(x2, w, b).view(*lead, N)
+        if b is None:
+            torch.mm(x2, w.t(), out=out)
+        else:
+            torch.addmm(b, x2, w.t(), out=out)
+        return out.view(*lead, N) if out.is_contiguous() else out.unflatten(0, lead)
+    if x2.stride(1) != 1 or x2.stride(0) % 8 or (M > 1 and x2.stride(0) < K) or \
+            x2.data_ptr() % 16:
+        x2 = x2.contiguous()
+    if out is None:
+        out = torch.empty((M, N), device=x.device, dtype=torch.bfloat16)
+    ldy = out.stride(0) if M > 1 else N
+    if ldy % 8 or out.data_ptr() % 16:
+        raise ValueError(f"{op}: out needs 16-byte aligned rows (row stride % 8 == 0)")
+    if b is not None:
+        b = b.contiguous()
+        if b.data_ptr() % 16:
+            b = b.clone()
+    L = _lib.lib()
+    nws = L.ra_linear_w4_work(M, N, K, S)
+    ws = torch.empty(nws, device=x.device, dtype=torch.float32) if nws else None
+    check(L.ra_linear_w4(ptr(x2), x2.stride(0) if M > 1 else K, ptr(q), ptr(s), ptr(b), ptr(out),
+                         ldy, ptr(ws), M, N, K, S, stream_ptr()), op)
+    return out.view(*lead, N) if out.is_contiguous() else out.unflatten(0, lead)
+
+
 def slot_advance(tok, lens, n_out, max_new, active, out, eos_token_id=None):
     """The continuous-batching engine's bookkeeping after the sampler, one launch, IN
     PLACE: an active slot with ``n_out[s] < cap`` stores ``out[s, n_out[s]] = tok[s]``,

@@ -408,6 +408,67 @@ def linear_w8(x, q, s, b=None):
     return F.linear(x, dequant_w8(q, s, x.dtype), b)
 
 
+# e2m1: sign bit, then the 3-bit code of these magnitudes
+_E2M1 = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+
+
+def _e8m0(s):
+    """``2^(s - 127)`` in fp32 for scale bytes in [1, 254]: the float with the bits ``s << 23``
+    (what the kernel hands its convert instruction)."""
+    return (s.to(torch.int32) << 23).view(torch.float32)
+
+
+def quantize_w4(w):
+    """OCP MXFP4 of a weight ``w`` [N, K], K % 32 == 0: ``(q uint8 [N, K/2], s uint8
+    [N, K/32])``. Byte j of a row of ``q`` holds element k = 2j in its low nibble and k = 2j + 1
+    in its high nibble; a nibble is e2m1 (sign bit, then the code of {0, 0.5, 1, 1.5, 2, 3, 4,
+    6}). ``s`` is e8m0: block g of a row, k in [32g, 32g + 32), has the scale ``2^(s - 127)``.
+
+    Per block, in fp32: ``e`` is the smallest integer with ``6 * 2^e >= max|w|`` (from
+    ``frexp``, exact), so nothing saturates; ``s = clamp(e + 127, 1, 254)``; every element is
+    ``w / 2^(s - 127)`` rounded to the nearest grid value, ties to the code with mantissa bit 0
+    (0.25 -> 0, 0.75 -> 1, 1.25 -> 1, 1.75 -> 2, 2.5 -> 2, 3.5 -> 4, 5 -> 4). An all-zero block
+    gets ``s = 127`` and zero nibbles. The sign bit of ``w`` is kept as it is: a negative value
+    that rounds to zero, and -0.0, are stored as code 8 (negative zero). Plain torch: it runs
+    once per weight."""
+    if not isinstance(w, torch.Tensor) or w.dim() != 2 or not w.is_floating_point() or \
+            w.shape[1] % 32 or w.shape[1] == 0:
+        raise ValueError(f"quantize_w4: w must be a floating [N, K] tensor with K % 32 == 0, got "
+                         f"{tuple(w.shape) if isinstance(w, torch.Tensor) else w!r}")
+    N, K = w.shape
+    blk = w.detach().float().view(N, K // 32, 32)
+    amax = blk.abs().amax(dim=2)
+    m, x = torch.frexp(amax)  # amax = m * 2^x, m in [0.5, 1): 6 * 2^(x - 3) = 0.75 * 2^x
+    e = torch.where(m <= 0.75, x - 3, x - 2)
+    s = torch.where(amax > 0, (e + 127).clamp(1, 254), torch.full_like(e, 127)).to(torch.uint8)
+    a = (blk.abs() / _e8m0(s)[:, :, None]).clamp_(max=6.0)
+    code = ((a > 0.25).to(torch.uint8) + (a >= 0.75) + (a > 1.25) + (a >= 1.75) + (a > 2.5)
+            + (a >= 3.5) + (a > 5.0)).to(torch.uint8)
+    nib = (code | (torch.signbit(blk).to(torch.uint8) << 3)).view(N, K)
+    q = nib[:, 0::2] | (nib[:, 1::2] << 4)
+    return q.contiguous(), s.contiguous()
+
+
+def dequant_w4(q, s, dtype=torch.bfloat16):
+    """``w[n, k] = e2m1(nibble k of q[n]) * 2^(s[n, k // 32] - 127)`` in ``dtype``, [N, K] for
+    ``q`` uint8 [N, K/2] and ``s`` uint8 [N, K/32] (``quantize_w4``'s layout; scale bytes in
+    [1, 254]). Exact in bf16 for every code and every scale byte in [3, 254]
+    (ops/csrc/linear_w4.hip)."""
+    N, K = q.shape[0], 2 * q.shape[1]
+    lut = torch.tensor(_E2M1 + tuple(-v for v in _E2M1), device=q.device)
+    nib = torch.stack([q & 15, q >> 4], dim=2).view(N, K)
+    val = lut[nib.long()].view(N, K // 32, 32)
+    return (val * _e8m0(s)[:, :, None]).view(N, K).to(dtype)
+
+
+def linear_w4(x, q, s, b=None):
+    """Weight-only MXFP4 linear (ops/csrc/linear_w4.hip semantics): ``x`` [..., K], ``q`` uint8
+    [N, K/2], ``s`` uint8 [N, K/32], ``b`` [N] or None. ``y[m, n] = sum_k x[m, k] * dq[n, k] +
+    b[n]``; the kernel sums in fp32 and rounds once, here it is ``F.linear`` on the weight
+    dequantised to x's dtype."""
+    return F.linear(x, dequant_w4(q, s, x.dtype), b)
+
+
 _MASK64 = (1 << 64) - 1
 
 

@@ -253,8 +253,8 @@ def _logprob_fields(lp, ids, tlp, m):
 
 
 def _checked_weights(weights):
-    if weights not in (None, "int8"):
-        raise ValueError(f"weights must be None or 'int8', got {weights!r}")
+    if weights not in (None, "int8", "mxfp4"):
+        raise ValueError(f"weights must be None, 'int8' or 'mxfp4', got {weights!r}")
 
 
 def _checked_kv_cache(kv_cache):
@@ -292,8 +292,8 @@ class GPT2Server:
             model.load_state_dict(torch.load(state_dict_path, map_location="cpu"))
         if self.device.type == "cuda":
             model = model.to(self.device, torch.bfloat16)
-        if weights == "int8":
-            model.quantize_weights()
+        if weights is not None:
+            model.quantize_weights(fmt=weights)
         self.model = model.eval()
         self.seed = seed
         self._generate_batch.set_max_batch_size(int(max_batch_size))
@@ -591,8 +591,8 @@ class GPT2EngineServer:
             if self.device.type == "cuda":
                 torch.cuda.set_device(self.device)
                 model = model.to(self.device, torch.bfloat16)
-            if self._weights == "int8":
-                model.quantize_weights()
+            if self._weights is not None:
+                model.quantize_weights(fmt=self._weights)
             kw = {} if poll_every is None else {"poll_every": int(poll_every)}
             if self._adapters:
                 from ray_amd.models.lora import LoRAStack
@@ -822,7 +822,9 @@ def build_gpt2_app(config="small", state_dict_path=None, seed=0, max_batch_size=
     ``"no_repeat_ngram_size"``, and a request may name them; the static server needs no option
     (``"stop"`` needs ``eos_token_id`` on both). ``weights="int8"`` (both servers): the model
     runs its linears and LM head on weight-only int8 copies (``GPT2.quantize_weights``), which
-    halves the weight bytes a decode step reads; None keeps the bf16 weights.
+    halves the weight bytes a decode step reads; ``weights="mxfp4"`` keeps OCP MXFP4 copies
+    instead (e2m1 with one power-of-two scale per 32 k, ``quantize_weights(fmt="mxfp4")``),
+    0.27x the bf16 weight bytes at a coarser grid; None keeps the bf16 weights.
     ``kv_cache="int8"`` (both servers; composes with ``weights``): K and V are cached as int8
     with one fp32 scale per vector, 0.53x the cache bytes (``generate(kv_cache=)`` /
     ``GPT2Engine(kv_cache=)``); with ``continuous=True`` it does not go with ``prefixes``,
