@@ -373,6 +373,9 @@ __global__ __launch_bounds__(256) void ln_bwd2_kernel(
   }
 }
 
+// VPL = ceil(D / 256) vectors per lane. Only 1..8, 12 and 16 are instantiated; a count in
+// between runs the next instantiated one (the forward and the v1 backward guard every
+// column against D, so the spare vectors do nothing). D > 4096 is refused.
 #define LN_DISPATCH(MACRO)                       \
   switch ((D + 255) / 256) {                     \
     case 1: MACRO(1); break;                     \
@@ -383,7 +386,9 @@ __global__ __launch_bounds__(256) void ln_bwd2_kernel(
     case 6: MACRO(6); break;                     \
     case 7: MACRO(7); break;                     \
     case 8: MACRO(8); break;                     \
+    case 9: case 10: case 11:                    \
     case 12: MACRO(12); break;                   \
+    case 13: case 14: case 15:                   \
     case 16: MACRO(16); break;                   \
     default: return hipErrorInvalidValue;        \
   }

@@ -48,6 +48,11 @@ def _ln_forward(x, w, b, eps):
     D = x.shape[-1]
     x2 = x.contiguous().view(-1, D)
     N = x2.shape[0]
+    if D > 4096:
+        # wider than the row the kernels hold in registers (ra_layernorm_fwd refuses it; no
+        # model here is that wide): the reference, and its statistics for the backward
+        var, mean = torch.var_mean(x2.float(), 1, unbiased=False)
+        return x2, ref.layer_norm(x2, w, b, eps), mean, torch.rsqrt(var + eps)
     y = torch.empty_like(x2)
     mean = torch.empty(N, device=x.device, dtype=torch.float32)
     rstd = torch.empty(N, device=x.device, dtype=torch.float32)
@@ -62,9 +67,6 @@ def _ln_backward(dy, x2, w, b, mean, rstd, dres=None, rbias=None):
     Returns (dx, dw, db, drbias) with None for gradients accumulated in place."""
     N, D = x2.shape
     dy2 = dy.contiguous().view(N, D)
-    L = _lib.lib()
-    work = torch.empty(L.ra_layernorm_bwd_work(N, D), device=dy.device, dtype=torch.float32)
-    dx = torch.empty_like(x2)
     params = [w, b] + ([rbias] if rbias is not None else [])
     sinks = [_grad_sink(p) for p in params]
     direct = all(s_ is not None for s_ in sinks)
@@ -73,9 +75,28 @@ def _ln_backward(dy, x2, w, b, mean, rstd, dres=None, rbias=None):
         outs.append(None)
     flags = (1 if outs[0].dtype == torch.bfloat16 else 0) | (2 if direct else 0)
     dr = None if dres is None else dres.contiguous().view(N, D)
-    check(L.ra_layernorm_bwd(ptr(dy2), ptr(x2), ptr(w), ptr(mean), ptr(rstd), ptr(dr), ptr(dx),
-                             ptr(outs[0]), ptr(outs[1]), ptr(outs[2]), ptr(work), N, D, flags,
-                             stream_ptr()), "layernorm_bwd")
+    if D > 4096:
+        # the rows _ln_forward handed to the reference: the same sums in fp32 torch, each
+        # result rounded once, into the same sinks
+        d32 = dy2.float()
+        xh = (x2.float() - mean[:, None]) * rstd[:, None]
+        wd = d32 * w.float()
+        dx32 = (wd - wd.mean(1, keepdim=True)
+                - xh * (wd * xh).mean(1, keepdim=True)) * rstd[:, None]
+        if dr is not None:
+            dx32 += dr.float()
+        for o, g in zip(outs, [(d32 * xh).sum(0), d32.sum(0), dx32.sum(0)]):
+            if o is not None:
+                o.add_(g) if direct else o.copy_(g)
+        dx = dx32.to(x2.dtype)
+    else:
+        L = _lib.lib()
+        work = torch.empty(L.ra_layernorm_bwd_work(N, D), device=dy.device,
+                           dtype=torch.float32)
+        dx = torch.empty_like(x2)
+        check(L.ra_layernorm_bwd(ptr(dy2), ptr(x2), ptr(w), ptr(mean), ptr(rstd), ptr(dr),
+                                 ptr(dx), ptr(outs[0]), ptr(outs[1]), ptr(outs[2]), ptr(work),
+                                 N, D, flags, stream_ptr()), "layernorm_bwd")
     if direct:
         for p in params:
             _grad_done(p)
@@ -128,13 +149,16 @@ class _ResidualLayerNorm(torch.autograd.Function):
         h2 = h.contiguous().view(-1, D)
         s2 = skip.contiguous().view(-1, D)
         N = h2.shape[0]
-        xo = torch.empty_like(h2)
-        y = torch.empty_like(h2)
-        mean = torch.empty(N, device=h.device, dtype=torch.float32)
-        rstd = torch.empty(N, device=h.device, dtype=torch.float32)
-        check(_lib.lib().ra_residual_layernorm_fwd(ptr(h2), ptr(rbias), ptr(s2), ptr(xo), ptr(w),
-                                                   ptr(b), ptr(y), ptr(mean), ptr(rstd), N, D,
-                                                   eps, stream_ptr()), "residual_layernorm_fwd")
+        if D > 4096:  # see _ln_forward
+            xo, y, mean, rstd = _ln_forward(ref.bias_residual(h2, rbias, s2), w, b, eps)
+        else:
+            xo = torch.empty_like(h2)
+            y = torch.empty_like(h2)
+            mean = torch.empty(N, device=h.device, dtype=torch.float32)
+            rstd = torch.empty(N, device=h.device, dtype=torch.float32)
+            check(_lib.lib().ra_residual_layernorm_fwd(
+                ptr(h2), ptr(rbias), ptr(s2), ptr(xo), ptr(w), ptr(b), ptr(y), ptr(mean),
+                ptr(rstd), N, D, eps, stream_ptr()), "residual_layernorm_fwd")
         ctx.save_for_backward(xo, w, mean, rstd)
         ctx.b, ctx.rbias = b, rbias
         ctx.shape = h.shape
